@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """G+D train-step throughput of the MI355X-native SP-GAN hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step and the run's configuration).  `--full` adds every measurement that is not the headline: the entries listed below,
+`literal_loop`, `split_bf16` and `hbm_traffic`.  They run after the timed region, except the device stamps of `roofline`, which
+are captured into the replayed step (GraphStamps).
+`--dump-outputs DIR` writes what the timed path hands its caller after its last timed step -- the step's returned losses and
+accuracies and both networks' state (parameters, BatchNorm running statistics) -- as DIR/<name>.npy, before anything else runs;
+the inputs and the initialisation are seeded, so two builds can be compared output for output.
 
 `--gpus N` with N > 1 launches its own N ranks (one process per GPU, re-executing this file under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`); started under torchrun
@@ -12,7 +20,7 @@ with both Adam updates (and, for N>1, both flat gradient all-reduces), on BASELI
 Chair-shaped synthetic clouds, 2048 points, per-GPU batch 32, WGAN loss + gradient penalty (lambda 10),
 fp32.  Weak scaling: the per-GPU batch is fixed, global batch = 32*N.  Inputs are resident in HBM.
 
-The JSON line also carries
+With `--full` the JSON line also carries
   roofline      : the dominant kernel (the fp32-MFMA gemm_nt), its algorithmic FLOPs per launch / average
                   launch time measured with HIP events on the launch stream, against the 157.3 TFLOP/s fp32 matrix peak;
   mfma          : FLOPs the step actually issues on the matrix cores (our formulation, padded tiles), the summed duration of
@@ -596,11 +604,35 @@ def time_steps(tr, step_fn, steps, dist_on, dev):
     return dt, t_issue
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, info, G, D):
+    """--dump-outputs: the tensors the last timed step returned (losses, accuracies) and the state both networks were left in
+    (G.<key> / D.<key> of their state_dicts), one DIR/<name>.npy each; float32 stays float32, everything else is written as float64."""
+    import numpy as np
+    arrays = {k: v for k, v in sorted(info.items()) if torch.is_tensor(v)}
+    arrays.update({"G." + k: v for k, v in G.state_dict().items()})
+    arrays.update({"D." + k: v for k, v in D.state_dict().items()})
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32 if v.dtype == torch.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)        # SURVEY 8(d): >= 50 timed steps after >= 10 warm-up steps
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: roofline and MFMA accounting, the comparison legs, the split-bf16 "
+                         "step, the CPU baseline (--no-extra-legs / --no-cpu-baseline leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's returned tensors and both networks' state as DIR/<name>.npy")
     ap.add_argument("--config", choices=("c2", "c4", "c5"), default="c2",
                     help="BASELINE config whose per-GPU shape is timed: c2 = configs[1] (N=2048, batch 32, fp32; default, the headline), "
                          "c4 = configs[3] per GPU (N=4096, batch 16), c5 = configs[4] per GPU (N=2048, batch 32, fp16 MFMA operands)")
@@ -617,6 +649,8 @@ def main():
     ap.add_argument("--variant", default="", help="comma-separated non-default generator flags (attn, eql, use_head, off, z_norm) or "
                     "small_d: times that variant instead of the headline configuration (SURVEY 8(f) N4); the JSON line says so")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.config == "c5":
         if args.mfma not in ("f32", "f16"):
             raise SystemExit("--config c5 is the fp16-operand mode (--mfma f16)")
@@ -665,13 +699,17 @@ def main():
     x, real, zs, alpha = make_inputs(dev, rank, PER_GPU_BATCH)
 
     def measure(overlap=None):
-        """Fresh models (same initialisation), prime + capture, W warm-up steps, K timed steps.  overlap: None = TrainStep's default."""
+        """Fresh models (same initialisation), prime + capture, W warm-up steps, K timed steps.  overlap: None = TrainStep's default.
+        Also returns what the last step returned (its info dict)."""
         G_, D_ = build_models(dev, variant)
         tr_ = spgan.TrainStep(G_, D_, gan="wgan", use_gp=True, lambda_gp=10.0, lr_g=1e-4, lr_d=1e-4, distributed=dist_on, graph=use_graph,
                               graph_warmup=graph_warmup, reference_schedule=args.reference_schedule)
         if overlap is not None:
             tr_.overlap_g_forward = bool(overlap)
-        step_ = lambda i: tr_.step(x, real, zs[(2 * i) % 4], zs[(2 * i + 1) % 4], alpha=alpha)
+        last = {}
+
+        def step_(i):
+            last["info"] = tr_.step(x, real, zs[(2 * i) % 4], zs[(2 * i + 1) % 4], alpha=alpha)
         if use_graph:
             if stamps is not None:
                 spgan.ops.launch_timer = stamps   # the dominant kernel's launches are captured between device-timestamp launches (GraphStamps)
@@ -685,10 +723,10 @@ def main():
         if overlap and os.environ.get("SPGAN_BENCH_TEST_HANG", "") == "overlap":      # test hook: the overlapped schedule never returns
             time.sleep(1e6)
         dt_, t_issue_ = time_steps(tr_, step_, args.steps, dist_on, dev)
-        return G_, D_, tr_, dt_, t_issue_
+        return G_, D_, tr_, dt_, t_issue_, last["info"]
 
     peak = PEAK_OF_MODE[args.mfma]
-    acct = MfmaAccounting(PER_GPU_BATCH * N_POINTS, peak, args.mfma) if (rank == 0 and not SELFTEST) else None
+    acct = MfmaAccounting(PER_GPU_BATCH * N_POINTS, peak, args.mfma) if (args.full and rank == 0 and not SELFTEST) else None
     stamps = GraphStamps(acct, dev) if (acct is not None and use_graph and os.environ.get("SPGAN_BENCH_STAMPS", "1") != "0") else None
     contact, dp_seq, wd = None, None, None
 
@@ -710,33 +748,35 @@ def main():
         wd = _Watchdog(rank)
         contact = first_contact(dev, rank, world, variant, wd, seconds)
         wd.arm("sequential schedule: capture, warm-up and the timed steps", seconds)
-        G, D, tr, dt, t_issue = measure(overlap=False)
+        G, D, tr, dt, t_issue, info = measure(overlap=False)
         wd.disarm()
         dp_seq = {"ms_per_step": round(dt / args.steps * 1e3, 3), "shapes_per_s": round(PER_GPU_BATCH * world * args.steps / dt, 2)}
         if contact["overlap_ok"] and os.environ.get("SPGAN_DP_OVERLAP", "1") != "0":
             wd.fallback = lambda phase: basic_line(dp_seq, "sequential", "sequential schedule measured in full; '%s' did not complete within %.0f s" % (phase, seconds))
             wd.arm("overlapped schedule (generator forward under D's all-reduce): capture, warm-up and the timed steps", seconds)
-            G2_, D2_, tr2_, dt2_, ti2_ = measure(overlap=True)
+            G2_, D2_, tr2_, dt2_, ti2_, info2_ = measure(overlap=True)
             wd.disarm()
             wd.fallback = None
             del G, D, tr
-            G, D, tr, dt, t_issue = G2_, D2_, tr2_, dt2_, ti2_
+            G, D, tr, dt, t_issue, info = G2_, D2_, tr2_, dt2_, ti2_, info2_
             dp_schedule = "overlapped"
         else:
             dp_schedule = "sequential"
             if "dp_fallback" not in contact and os.environ.get("SPGAN_DP_OVERLAP", "1") == "0":
                 contact["dp_fallback"] = "sequential schedule: SPGAN_DP_OVERLAP=0"
     else:
-        G, D, tr, dt, t_issue = measure()
+        G, D, tr, dt, t_issue, info = measure()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, info, G, D)       # before the accounting steps below advance the same networks
 
     in_graph = stamps.result(peak) if stamps is not None else None
-    if wd is not None:
+    if wd is not None and args.full:
         # the phases after the timed region (eager accounting steps with their own collectives) run under the deadline too: what is measured is kept
         final_m = {"ms_per_step": round(dt / args.steps * 1e3, 3), "shapes_per_s": round(PER_GPU_BATCH * world * args.steps / dt, 2)}
         wd.fallback = lambda phase: basic_line(final_m, dp_schedule, "timed region complete; '%s' did not complete within %.0f s" % (phase, seconds))
         wd.arm("accounting steps after the timed region", seconds)
     ACCT_STEPS = 4
-    if not SELFTEST:
+    if args.full and not SELFTEST:
         # a replayed graph offers no per-launch hook: the matrix-core launches are bracketed with HIP events over a few eager steps
         # of the same TrainStep right after the timed region (same process, same tensors; not part of `value`).  Data-parallel:
         # every rank runs them (the all-reduces inside must match up); only rank 0 records.
@@ -751,7 +791,8 @@ def main():
     drop_in = None
     if wd is not None:
         wd.disarm()
-    if not SELFTEST and not args.no_extra_legs and not variant and world == 1:      # comparison legs: single-GPU runs only (nothing after the timed region may cost a multi-GPU line)
+    extra_legs = args.full and not args.no_extra_legs
+    if not SELFTEST and extra_legs and not variant and world == 1:      # comparison legs: single-GPU runs only (nothing after the timed region may cost a multi-GPU line)
         # The same step as an unmodified reference loop would drive it (model.py:246-248,272-273): z tiled to [B,N,nz], the G step's
         # unused D(real) forward evaluated, EdgeConv1 on every copy of the tiled sphere.  Fresh models (same initialisation), its own
         # captured graph; every rank takes part.
@@ -770,7 +811,7 @@ def main():
         del tr2, G2, D2, zt
 
     literal = None
-    if not SELFTEST and not args.no_extra_legs and not variant and world == 1:
+    if not SELFTEST and extra_legs and not variant and world == 1:
         # The reference's loop body EXECUTED LITERALLY (examples/reference_loop.py: model.py:239-279 statement for statement -- separate G() /
         # D() calls, requires_grad toggles, dis_loss / gen_loss, .backward(), torch.optim.Adam) on the HIP modules, latent tiled
         # [B,N,128]; no TrainStep.  (a) issued eagerly from Python, (b) the same function under spgan.CapturedBody (the caller's own
@@ -801,7 +842,7 @@ def main():
         del G3, D3, body, st3
 
     split = None
-    if not SELFTEST and not args.no_extra_legs and not variant and world == 1 and args.mfma == "f32" and rank == 0:
+    if not SELFTEST and extra_legs and not variant and world == 1 and args.mfma == "f32" and rank == 0:
         # The SAME step with the split-bf16 products (`--mfma bf16x3`): fresh models (same initialisation), its own captured graph, 20 timed
         # steps after priming, then the matrix-core accounting of that mode over 4 eager steps.  Reported beside the fp32 headline, not as it.
         spgan.ops.set_mfma_operands("bf16x3")
@@ -886,7 +927,7 @@ def main():
             line["literal_loop"] = literal
         if split is not None:
             line["split_bf16"] = split
-        if world == 1 and not args.no_cpu_baseline and not SELFTEST:
+        if world == 1 and args.full and not args.no_cpu_baseline and not SELFTEST:
             line["cpu_baseline"] = cpu_baseline()
             line["speedup_vs_cpu_baseline"] = round(shapes_s / line["cpu_baseline"]["value"], 1)
         print(json.dumps(line), flush=True)

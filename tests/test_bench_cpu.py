@@ -38,6 +38,29 @@ def test_bench_self_launches_its_ranks(n):
         assert line["collective_backend"] == "gloo"
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's returned tensors and both networks' state as float32 / float64 .npy files (<= 64 MB);
+    the inputs are seeded, so two runs with the same arguments write the same arrays (the CPU doubles are deterministic)."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = _run(["--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _json_lines(r.stdout)[0]
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == sorted(p.name for p in dirs[1].iterdir())
+    assert {"loss_d.npy", "loss_g.npy", "D.fc2.0.weight.npy"} <= set(names) and any(n.startswith("G.") for n in names)
+    total = 0
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert _run(["--steps", "0"]).returncode != 0
+
+
 def test_bench_eight_ranks():
     """`python bench.py --gpus 8` -- the driver's scaling run -- as a plumbing self-test: eight gloo ranks on this host, the line
     reports world size 8, global batch 8 x the per-rank batch, weak scaling."""

@@ -34,3 +34,26 @@ def test_two_rank_schedule_on_one_gpu():
     fc = line["first_contact"]
     assert line["rccl_ranks_seen"] == 2 and fc["schedules_bit_equal"] is True and fc["ranks_bit_equal"] is True
     assert line["dp_schedule"] == "overlapped" and "dp_fallback" not in line and line["dp_sequential_schedule"]["ms_per_step"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """`python bench.py --gpus 1` without --full: only the headline (no roofline, accounting, comparison legs or CPU baseline), K timed
+    steps, and `--dump-outputs` leaves the last timed step's losses and both networks' state, all finite."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SPGAN_BENCH_SELFTEST", "SPGAN_DIST_BACKEND"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "f32" and line["hipgraph_replay"] is True
+    assert not {"roofline", "mfma", "drop_in_caller", "literal_loop", "split_bf16", "cpu_baseline", "hbm_traffic"} & set(line)
+    names = {p.name for p in out.iterdir()}
+    assert {"loss_d.npy", "loss_g.npy", "D.fc2.0.weight.npy"} <= names
+    for n in names:
+        a = np.load(out / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n

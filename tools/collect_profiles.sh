@@ -7,11 +7,11 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python $R/bench.py --config c5 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_f16_operands.json 2>> $O/${TAG}_bench.err      # c5 = --mfma f16
-python $R/bench.py --config c4 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_c4.json 2>> $O/${TAG}_bench.err                # N = 4096, per-GPU batch 16
-python $R/bench.py --mfma bf16x3 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_bf16x3.json 2>> $O/${TAG}_bench.err
-rm -rf /tmp/prof_s; rocprofv3 --kernel-trace --stats -d /tmp/prof_s -o r -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs > /tmp/bench_s.log 2>&1
+python $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python $R/bench.py --full --config c5 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_f16_operands.json 2>> $O/${TAG}_bench.err      # c5 = --mfma f16
+python $R/bench.py --full --config c4 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_c4.json 2>> $O/${TAG}_bench.err                # N = 4096, per-GPU batch 16
+python $R/bench.py --full --mfma bf16x3 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_bf16x3.json 2>> $O/${TAG}_bench.err
+rm -rf /tmp/prof_s; rocprofv3 --kernel-trace --stats -d /tmp/prof_s -o r -- python $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs > /tmp/bench_s.log 2>&1
 DB=$(find /tmp/prof_s -name "*.db" | head -1)
 python $R/tools/rocprof_summary.py $DB 31 > $O/${TAG}_bench_kernel_stats.txt
 python $R/tools/roofline_same_process.py /tmp/bench_s.log $DB > $O/${TAG}_roofline_same_process.json 2>> $O/${TAG}_bench.err      # stamps / events / rocprof of ONE process      # 31 steps: 4 priming + 3 warm-up + 20 timed + 4 eager accounting steps (+ the keep-busy launches: the Cijk_ row)
@@ -37,19 +37,19 @@ python $R/tools/nt3_ksweep.py > $O/${TAG}_nt3_ksweep.txt 2>/dev/null
 bash $R/tools/nt3_trace.sh > $O/${TAG}_nt3_trace.txt 2>/dev/null
 python $R/tools/tn3_bench.py > $O/${TAG}_tn3_bench.txt 2>/dev/null                   # split-bf16 weight gradients (csrc/gemm_tn_wide3.hip) against the fp32 kernel
 (cd /tmp && python $R/tools/nt16_bench.py) > $O/${TAG}_nt16_bench.txt 2>/dev/null     # fp16 operands: row-pipelined 256 x 256 tiles (csrc/gemm_wide16.hip) against gemm_wide.hip's
-python $R/bench.py --mfma bf16x3 --config c4 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_c4_bf16x3.json 2>/dev/null      # the C4 per-GPU shape in the split mode
-SPGAN_TN_SPLIT=0 python $R/bench.py --mfma bf16x3 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_bf16x3_tn_f32.json 2>/dev/null      # A/B: weight gradients on the fp32 kernel
-SPGAN_NT_WIDE16=0 python $R/bench.py --config c5 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_f16_operands_old_wide.json 2>/dev/null   # A/B: gemm_wide.hip's fp16 form
+python $R/bench.py --full --mfma bf16x3 --config c4 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_c4_bf16x3.json 2>/dev/null      # the C4 per-GPU shape in the split mode
+SPGAN_TN_SPLIT=0 python $R/bench.py --full --mfma bf16x3 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_bf16x3_tn_f32.json 2>/dev/null      # A/B: weight gradients on the fp32 kernel
+SPGAN_NT_WIDE16=0 python $R/bench.py --full --config c5 --no-cpu-baseline --no-extra-legs > $O/${TAG}_bench_f16_operands_old_wide.json 2>/dev/null   # A/B: gemm_wide.hip's fp16 form
 bash $R/tools/nt3_pmc.sh > $O/${TAG}_nt3_pmc.txt 2>/dev/null
 python $R/tools/exp/nt3_power_probe.py > $O/${TAG}_nt3_power_probe.txt 2>/dev/null
 python $R/tools/exp/nt3_accuracy_probe.py > $O/${TAG}_nt3_accuracy_probe.txt 2>/dev/null
 python $R/tools/exp/argmax_flip_probe.py > $O/${TAG}_argmax_flip_probe.txt 2>/dev/null
-rm -rf /tmp/prof_b3; rocprofv3 --kernel-trace --stats -d /tmp/prof_b3 -o r -- python $R/bench.py --mfma bf16x3 --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs > /tmp/bench_b3.log 2>&1
+rm -rf /tmp/prof_b3; rocprofv3 --kernel-trace --stats -d /tmp/prof_b3 -o r -- python $R/bench.py --full --mfma bf16x3 --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs > /tmp/bench_b3.log 2>&1
 python $R/tools/rocprof_summary.py $(find /tmp/prof_b3 -name "*.db" | head -1) 31 > $O/${TAG}_bench_bf16x3_kernel_stats.txt
 python $R/tools/step_sequence.py $(find /tmp/prof_b3 -name "*.db" | head -1) -8 > $O/${TAG}_step_sequence_bf16x3.txt
 (python $R/tools/knn_ab.py 2048 32; python $R/tools/knn_ab.py 4096 16) > $O/${TAG}_knn_ab.txt 2>&1
 python $R/tools/dual_bench.py > $O/${TAG}_dual_bench.txt 2>/dev/null
-rm -rf /tmp/prof_c4; rocprofv3 --kernel-trace --stats -d /tmp/prof_c4 -o r -- python $R/bench.py --config c4 --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs > /tmp/bench_c4.log 2>&1
+rm -rf /tmp/prof_c4; rocprofv3 --kernel-trace --stats -d /tmp/prof_c4 -o r -- python $R/bench.py --full --config c4 --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs > /tmp/bench_c4.log 2>&1
 python $R/tools/rocprof_summary.py $(find /tmp/prof_c4 -name "*.db" | head -1) 31 > $O/${TAG}_bench_c4_kernel_stats.txt
 bash $R/tools/profile_f16.sh $TAG > /dev/null 2>&1      # kernel table of the "f16" operand mode
 python $R/tools/step_sequence.py $(find /tmp/prof_h -name "*.db" | head -1) -8 > $O/${TAG}_step_sequence_f16.txt      # ... and its ordered step sequence

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/prof_h; rocprofv3 --kernel-trace --stats -d /tmp/prof_h -o r -- python $R/bench.py --mfma f16 --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs > /tmp/bench_h.log 2>&1
+rm -rf /tmp/prof_h; rocprofv3 --kernel-trace --stats -d /tmp/prof_h -o r -- python $R/bench.py --full --mfma f16 --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs > /tmp/bench_h.log 2>&1
 tail -1 /tmp/bench_h.log | cut -c1-240
 DB=$(find /tmp/prof_h -name "*.db" | head -1)
 [ -n "$DB" ] || { echo "no rocprofv3 database"; exit 1; }
