@@ -747,6 +747,21 @@ int spgan_adam_step(float* p, const float* g, float* m, float* v, size_t n, floa
  * zero_grad != 0: g is zeroed after it was read -- the optimizer.zero_grad() of the next iteration (model.py:243,268) without a launch. */
 int spgan_adam_step_dev(float* p, float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                         float* state, float grad_scale, int zero_grad, spgan_stream_t s);
+/* Generator weight EMA (Common/network_utils.py:97-108): e <- a*e + (1-a)*p over a flat shadow buffer e of the same layout as p.
+ * a after the t-th update: ema_warmup != 0 -> min(1 - 1/t, ema_rate) (exp_mov_avg with global_step = t-1; t = 1 copies p exactly),
+ * ema_warmup == 0 -> ema_rate (accumulate).  a and 1-a are evaluated in double (ema_rate is a double, as the reference's Python scalar)
+ * and rounded once; the three entry points below share that formula and the per-element update, so for the same t, p and e they produce
+ * bit-equal shadows.  0 <= ema_rate <= 1.
+ * spgan_adam_ema_step_dev: spgan_adam_step_dev (same state, same zero_grad; p, m, v, g bit-identical to it, still two launches) with
+ * the EMA applied to the updated p inside the update launch; t = state[0] after this call's advance.
+ * spgan_adam_ema_step: the host-step twin of spgan_adam_step (p, m, v bit-identical to it), t = step.
+ * spgan_ema_update_dev: the EMA alone, for callers with their own optimiser; counter = one int32 on the device, advanced by this call
+ * (t = its value afterwards), so a captured hipGraph replays it. */
+int spgan_adam_ema_step_dev(float* p, float* g, float* m, float* v, float* e, size_t n, float lr, float beta1, float beta2, float eps,
+                            float* state, float grad_scale, int zero_grad, double ema_rate, int ema_warmup, spgan_stream_t s);
+int spgan_adam_ema_step(float* p, const float* g, float* m, float* v, float* e, size_t n, float lr, float beta1, float beta2, float eps,
+                        int step, float grad_scale, double ema_rate, int ema_warmup, spgan_stream_t s);
+int spgan_ema_update_dev(float* e, const float* p, size_t n, double ema_rate, int ema_warmup, int* counter, spgan_stream_t s);
 
 /* Measurement plumbing (bench.py's `roofline` entry): device timestamps that survive a hipGraph capture, where HIP events
  * cannot be queried.  spgan_stamp_begin stores the constant-rate wall clock in *slot; spgan_stamp_end adds (now - *slot) to acc2[0] and 1

@@ -1,6 +1,6 @@
 // HBM-bound per-point kernels: AdaIN (AdaptivePointNorm, Generation/Generator.py:24-45) forward and
 // backward, the sparse BatchNorm backward behind D's global max-pool (Discriminator.py:77-81,104),
-// max-pool gradient routing, tanh backward and the flat Adam update.  Lanes run along channels.
+// max-pool gradient routing, tanh backward, the flat Adam update and the generator weight EMA.  Lanes run along channels.
 #include "common.hpp"
 
 namespace {
@@ -486,6 +486,122 @@ __global__ void adam_dev_kernel(float* __restrict__ p, float* __restrict__ g, fl
   p[t] -= (lr / bc1) * (mm / denom);
 }
 
+// Generator weight EMA (Common/network_utils.py:97-108: `accumulate`, `exp_mov_avg`), standalone and fused into the flat Adam update.
+// The fused kernels apply the Adam step above (adam_kernel / adam_dev_kernel: the same per-element roundings, so p, m, v and g come
+// out bit-identical) and then e <- a*e + (1-a)*p_new while p_new is still in a register: one extra read and write of the
+// shadow buffer instead of a separate pass over both buffers.  Pure streaming: four elements per thread (16-byte accesses when every
+// pointer allows them), no LDS, no atomics.
+
+// The EMA coefficient a and 1 - a after the t-th update (t >= 1).  warmup: exp_mov_avg(..., global_step = t - 1), a = min(1 - 1/t, rate)
+// (a = 0 at t = 1: the shadow becomes a copy); otherwise accumulate's constant a = rate.  rate is a double and a, 1 - a are evaluated
+// in double and rounded once, as the reference's Python scalars are (1 - a from a float32 rate would be 1.3e-5 off for rate 0.999).
+// Host and device share this one definition: bit-equal coefficients for the host-step variant.
+__host__ __device__ inline void ema_coef(int t, double rate, int warmup, float* a, float* b) {
+  double ad = rate;
+  if (warmup) {
+    const double w = 1.0 - 1.0 / (double)(t < 1 ? 1 : t);
+    if (w < ad) ad = w;
+  }
+  *a = (float)ad;
+  *b = (float)(1.0 - ad);
+}
+
+// Contraction is spelled out below (fmaf, `fp contract(off)`): the compiler contracts the plain Adam kernels' expressions differently in
+// the two of them and would contract a vectorised copy differently again.  These are the roundings adam_dev_kernel (kDev) and
+// adam_kernel (!kDev) are compiled to on gfx950 -- they differ only in which product of m's update is fused -- so p, m and v come out
+// bit-identical (pinned by tests/test_ema_gpu.py).
+__device__ __forceinline__ float ema_elem(float e, float p, float a, float b) {
+#pragma clang fp contract(off)
+  return fmaf(a, e, b * p);
+}
+
+// step = lr / bc1 (the dev variant's lr already multiplied by state[3]).
+template <bool kDev>
+__device__ __forceinline__ void adam_elem(float& p, float& g, float& m, float& v, float step, float b1, float b2, float eps,
+                                          float rsqrt_bc2, float gscale) {
+#pragma clang fp contract(off)
+  const float gr = g * gscale;
+  const float mm = kDev ? fmaf(b1, m, (1.f - b1) * gr) : fmaf(1.f - b1, gr, b1 * m);
+  const float vv = b2 * v + gr * ((1.f - b2) * gr);
+  m = mm;
+  v = vv;
+  const float denom = fmaf(rsqrt_bc2, sqrtf(vv), eps);
+  p = fmaf(-step, mm / denom, p);
+}
+
+__device__ __forceinline__ float& at(f32x4& x, int k) { return reinterpret_cast<float*>(&x)[k]; }
+
+// Elements [4i, 4i+4) of one thread.  kVec: all five buffers 16-byte aligned (flat Adam buffers always are, optim.FlatParams).
+template <bool kVec, bool kAdam, bool kDev>
+__device__ __forceinline__ void adam_ema_body(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                              float* __restrict__ e, size_t n, float step, float b1, float b2, float eps,
+                                              float rsqrt_bc2, float gscale, int zero_grad, float a, float b) {
+  const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i >= n) return;
+  if (kVec && i + 4 <= n) {
+    f32x4 pp = *reinterpret_cast<const f32x4*>(p + i), ee = *reinterpret_cast<const f32x4*>(e + i);
+    if (kAdam) {
+      f32x4 gg = *reinterpret_cast<const f32x4*>(g + i), mm = *reinterpret_cast<const f32x4*>(m + i), vv = *reinterpret_cast<const f32x4*>(v + i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) adam_elem<kDev>(at(pp, k), at(gg, k), at(mm, k), at(vv, k), step, b1, b2, eps, rsqrt_bc2, gscale);
+      *reinterpret_cast<f32x4*>(m + i) = mm;
+      *reinterpret_cast<f32x4*>(v + i) = vv;
+      *reinterpret_cast<f32x4*>(p + i) = pp;
+      if (zero_grad) *reinterpret_cast<f32x4*>(g + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) at(ee, k) = ema_elem(at(ee, k), at(pp, k), a, b);
+    *reinterpret_cast<f32x4*>(e + i) = ee;
+    return;
+  }
+  for (size_t j = i; j < n && j < i + 4; ++j) {
+    float pj = p[j];
+    if (kAdam) {
+      float gj = g[j], mj = m[j], vj = v[j];
+      adam_elem<kDev>(pj, gj, mj, vj, step, b1, b2, eps, rsqrt_bc2, gscale);
+      m[j] = mj;
+      v[j] = vj;
+      p[j] = pj;
+      if (zero_grad) g[j] = 0.f;
+    }
+    e[j] = ema_elem(e[j], pj, a, b);
+  }
+}
+
+// Capturable: state as adam_dev_kernel reads it (advanced by adam_prep_kernel, launched in front); t = state[0] after the advance.
+template <bool kVec>
+__global__ void adam_ema_dev_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                    float* __restrict__ e, size_t n, float lr, float b1, float b2, float eps, const float* __restrict__ state,
+                                    float gscale, int zero_grad, double rate, int warmup) {
+  const float bc1 = state[1], rsqrt_bc2 = state[2];
+  lr *= state[3];
+  float a, b;
+  ema_coef(reinterpret_cast<const int*>(state)[0], rate, warmup, &a, &b);
+  adam_ema_body<kVec, true, true>(p, g, m, v, e, n, lr / bc1, b1, b2, eps, rsqrt_bc2, gscale, zero_grad, a, b);
+}
+
+// Host-step twin of adam_kernel: bias corrections and EMA coefficients computed by the caller.
+template <bool kVec>
+__global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                float* __restrict__ e, size_t n, float lr, float b1, float b2, float eps, float bc1, float rsqrt_bc2,
+                                float gscale, float a, float b) {
+  adam_ema_body<kVec, true, false>(p, const_cast<float*>(g), m, v, e, n, lr / bc1, b1, b2, eps, rsqrt_bc2, gscale, 0, a, b);
+}
+
+// Standalone update with its own device-side step count: ema_prep_kernel advances counter[0], ema_dev_kernel reads it.
+__global__ void ema_prep_kernel(int* __restrict__ counter) { counter[0] += 1; }
+
+template <bool kVec>
+__global__ void ema_dev_kernel(float* __restrict__ e, const float* __restrict__ p, size_t n, double rate, int warmup,
+                               const int* __restrict__ counter) {
+  float a, b;
+  ema_coef(counter[0], rate, warmup, &a, &b);
+  adam_ema_body<kVec, false, false>(const_cast<float*>(p), nullptr, nullptr, nullptr, e, n, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 0, a, b);
+}
+
+inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+inline dim3 grid4(size_t n) { return dim3(cdiv(cdiv((long)n, 4), 256)); }
+
 // Device timestamps INSIDE a replayed hipGraph (HIP events cannot be queried there): a one-thread launch in front of the kernel under
 // measurement stores the constant-rate wall clock (s_memrealtime; hipDeviceAttributeWallClockRate), a one-thread launch behind it adds
 // the elapsed ticks to an accumulator.  Stream order makes the pair bracket exactly that kernel (plus two launch boundaries: an EMPTY
@@ -914,5 +1030,50 @@ extern "C" int spgan_adam_step(float* p, const float* g, float* m, float* v, siz
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   hipLaunchKernelGGL(adam_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)s_, p, g, m, v, n, lr, beta1, beta2, eps, (float)bc1,
                      (float)(1.0 / sqrt(bc2)), grad_scale);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_adam_ema_step_dev(float* p, float* g, float* m, float* v, float* e, size_t n, float lr, float beta1, float beta2,
+                                       float eps, float* state, float grad_scale, int zero_grad, double ema_rate, int ema_warmup,
+                                       spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(p && g && m && v && e && state && n > 0);
+  SPGAN_CHECK_ARG(ema_rate >= 0.0 && ema_rate <= 1.0);
+  hipStream_t s = (hipStream_t)s_;
+  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(1), 0, s, beta1, beta2, state);      // the state advance of spgan_adam_step_dev
+  if (al16(p) && al16(g) && al16(m) && al16(v) && al16(e))
+    hipLaunchKernelGGL(adam_ema_dev_kernel<true>, grid4(n), dim3(256), 0, s, p, g, m, v, e, n, lr, beta1, beta2, eps, state, grad_scale,
+                       zero_grad, ema_rate, ema_warmup);
+  else
+    hipLaunchKernelGGL(adam_ema_dev_kernel<false>, grid4(n), dim3(256), 0, s, p, g, m, v, e, n, lr, beta1, beta2, eps, state, grad_scale,
+                       zero_grad, ema_rate, ema_warmup);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_adam_ema_step(float* p, const float* g, float* m, float* v, float* e, size_t n, float lr, float beta1, float beta2,
+                                   float eps, int step, float grad_scale, double ema_rate, int ema_warmup, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(p && g && m && v && e && n > 0 && step > 0);
+  SPGAN_CHECK_ARG(ema_rate >= 0.0 && ema_rate <= 1.0);
+  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);   // as spgan_adam_step
+  float a, b;
+  ema_coef(step, ema_rate, ema_warmup, &a, &b);
+  hipStream_t s = (hipStream_t)s_;
+  if (al16(p) && al16(g) && al16(m) && al16(v) && al16(e))
+    hipLaunchKernelGGL(adam_ema_kernel<true>, grid4(n), dim3(256), 0, s, p, g, m, v, e, n, lr, beta1, beta2, eps, (float)bc1,
+                       (float)(1.0 / sqrt(bc2)), grad_scale, a, b);
+  else
+    hipLaunchKernelGGL(adam_ema_kernel<false>, grid4(n), dim3(256), 0, s, p, g, m, v, e, n, lr, beta1, beta2, eps, (float)bc1,
+                       (float)(1.0 / sqrt(bc2)), grad_scale, a, b);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_ema_update_dev(float* e, const float* p, size_t n, double ema_rate, int ema_warmup, int* counter, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(e && p && counter && n > 0);
+  SPGAN_CHECK_ARG(ema_rate >= 0.0 && ema_rate <= 1.0);
+  hipStream_t s = (hipStream_t)s_;
+  hipLaunchKernelGGL(ema_prep_kernel, dim3(1), dim3(1), 0, s, counter);
+  if (al16(e) && al16(p))
+    hipLaunchKernelGGL(ema_dev_kernel<true>, grid4(n), dim3(256), 0, s, e, p, n, ema_rate, ema_warmup, counter);
+  else
+    hipLaunchKernelGGL(ema_dev_kernel<false>, grid4(n), dim3(256), 0, s, e, p, n, ema_rate, ema_warmup, counter);
   return spgan_launch_status();
 }

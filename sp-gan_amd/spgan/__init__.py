@@ -10,9 +10,9 @@ from . import dataset, fixture_rng, metrics, ops, pointnet_util, sampling  # noq
 from .capture import CapturedBody                                          # noqa: F401
 from .losses import GradientPenalty, dis_loss, gen_loss                    # noqa: F401
 from .modules import AdaptivePointNorm, Discriminator, EdgeBlock, Generator, get_edge_features   # noqa: F401
-from .optim import Adam, flatten_module                                    # noqa: F401
+from .optim import EMA, Adam, StepLR, flatten_module                       # noqa: F401
 from .parallel import DataParallel, init_process_group_from_env, shard_batch   # noqa: F401
 from .train import TrainStep, requires_grad                                # noqa: F401
 
 __all__ = ["Generator", "Discriminator", "EdgeBlock", "AdaptivePointNorm", "get_edge_features", "dis_loss", "gen_loss",
-           "GradientPenalty", "TrainStep", "CapturedBody", "Adam", "DataParallel", "requires_grad", "ops", "fixture_rng", "sampling"]
+           "GradientPenalty", "TrainStep", "CapturedBody", "Adam", "EMA", "StepLR", "DataParallel", "requires_grad", "ops", "fixture_rng", "sampling"]

@@ -304,6 +304,9 @@ SIGNATURES = {
     "spgan_axpby": (I, [F, P, F, P, SZ, P]),
     "spgan_adam_step": (I, [P, P, P, P, SZ, F, F, F, F, I, F, P]),
     "spgan_adam_step_dev": (I, [P, P, P, P, SZ, F, F, F, F, P, F, I, P]),
+    "spgan_adam_ema_step_dev": (I, [P, P, P, P, P, SZ, F, F, F, F, P, F, I, C.c_double, I, P]),
+    "spgan_adam_ema_step": (I, [P, P, P, P, P, SZ, F, F, F, F, I, F, C.c_double, I, P]),
+    "spgan_ema_update_dev": (I, [P, P, SZ, C.c_double, I, P, P]),
 }
 
 _lib = None

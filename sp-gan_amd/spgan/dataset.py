@@ -89,9 +89,18 @@ class DeviceDataset:
         self.gen = torch.Generator(device=self.device)
         if seed is not None:
             self.gen.manual_seed(seed)
+        self.epoch = 0                                                         # completed passes
 
     def __len__(self) -> int:
         return self.data.shape[0]
+
+    def get_state(self) -> dict:
+        """Resume state at an epoch boundary (between two complete passes): the generator's position and the epoch counter."""
+        return {"gen": self.gen.get_state(), "epoch": self.epoch}
+
+    def set_state(self, state: dict) -> None:
+        self.gen.set_state(state["gen"])
+        self.epoch = int(state["epoch"])
 
     @property
     def num_batches(self) -> int:
@@ -112,6 +121,7 @@ class DeviceDataset:
         order = torch.randperm(len(self), generator=self.gen, device=self.device)
         for b in range(self.num_batches):
             yield self.get_batch(order[b * self.batch_size:(b + 1) * self.batch_size])
+        self.epoch += 1
 
 
 class HostStagedLoader:
@@ -133,6 +143,7 @@ class HostStagedLoader:
         self.data = (scale * normalize_point_cloud(pts))[:, :num_points].contiguous().numpy()        # H5DataLoader.py:107, then :113
         self.num_points, self.batch_size, self.augment = num_points, batch_size, augment
         self.rng = np.random.default_rng(seed)
+        self.epoch = 0                                                         # completed passes
         cuda = self.device.type == "cuda"
         self._host = [torch.empty((batch_size, num_points, 3), dtype=torch.float32, pin_memory=cuda) for _ in range(2)]
         self._dev = [torch.empty((batch_size, num_points, 3), dtype=torch.float32, device=self.device) for _ in range(2)]
@@ -146,6 +157,14 @@ class HostStagedLoader:
     @property
     def num_batches(self) -> int:
         return len(self) // self.batch_size
+
+    def get_state(self) -> dict:
+        """Resume state at an epoch boundary (no batch staged ahead): the numpy generator's state and the epoch counter."""
+        return {"rng": self.rng.bit_generator.state, "epoch": self.epoch}
+
+    def set_state(self, state: dict) -> None:
+        self.rng.bit_generator.state = state["rng"]
+        self.epoch = int(state["epoch"])
 
     def _stage(self, slot: int, index: np.ndarray) -> None:
         B, P = self.batch_size, self.num_points
@@ -174,6 +193,7 @@ class HostStagedLoader:
         order = self.rng.permutation(len(self))
         nb, bs = self.num_batches, self.batch_size
         if nb == 0:
+            self.epoch += 1
             return
         self._stage(0, order[:bs])
         for b in range(nb):
@@ -191,3 +211,4 @@ class HostStagedLoader:
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream())
                     self._free[slot] = ev
+        self.epoch += 1

@@ -2284,3 +2284,9 @@ def adam_step_dev(p: Tensor, g: Tensor, m: Tensor, v: Tensor, state: Tensor, lr:
     if state.numel() != 4 or not state.is_contiguous():
         raise ValueError("adam_step_dev: state must be 4 contiguous floats (step bits, two bias corrections, lr multiplier)")
     check(_lib.load().spgan_adam_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, _p(state), grad_scale, 1 if zero_grad else 0, _s()), "adam_step_dev")
+
+
+
+# The generator-EMA entry points (spgan_adam_ema_step_dev / spgan_adam_ema_step / spgan_ema_update_dev): wrappers in ops_ema.py, part of
+# this module's namespace.  Their CPU doubles live beside the tests that use them (tests/ema_model.py), not among the kernel models.
+from .ops_ema import adam_ema_step, adam_ema_step_dev, ema_update_dev        # noqa: E402,F401

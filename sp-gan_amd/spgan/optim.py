@@ -5,9 +5,13 @@ parameter/gradient layout shared with the data-parallel reducer.
 pre-binds `.grad` to the matching slice of ONE gradient buffer: the optimiser update is a single
 HIP launch and the data-parallel all-reduce a single RCCL collective per network.
 state_dict() is unaffected (parameters keep their names/shapes).
+
+`EMA` is the generator weight average of Common/network_utils.py:97-108 over such a flat buffer; `Adam.attach_ema` folds its update
+into the optimiser's launch.
 """
 from __future__ import annotations
 
+import copy
 from typing import Iterable, List, Optional
 
 import torch
@@ -73,6 +77,7 @@ class Adam:
         self.capturable = capturable
         self.dev_state = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float32, device=self.fp.flat.device) if capturable else None
         self.base_lr = lr
+        self.ema: Optional["EMA"] = None          # attach_ema(): step() also advances this shadow, in the same launch
         # zero_grad_in_step (capturable mode; TrainStep): step() leaves the flat gradient buffer zeroed -- the kernel has every gradient in a
         # register anyway -- and the zero_grad() that follows it is a no-op instead of a fill launch.  Only for an owner that writes the
         # gradients exclusively between zero_grad() and step().
@@ -95,15 +100,36 @@ class Adam:
             return
         self.fp.zero_grad()
 
+    def attach_ema(self, ema: "EMA") -> None:
+        """From now on step() also updates `ema`'s shadow from the freshly updated parameters, inside the same launch
+        (ops.adam_ema_step_dev / adam_ema_step; the parameters, moments and gradients come out bit-identical to a step without it).
+        The shadow's warm-up position is then this optimiser's step count t."""
+        if ema.src.flat.data_ptr() != self.fp.flat.data_ptr():
+            raise ValueError("attach_ema: the EMA averages another module's parameters")
+        if ema._opt is not None and ema._opt is not self:
+            raise ValueError("attach_ema: the EMA is attached to another optimiser")
+        self.ema = ema
+        ema._opt = self
+
     def step(self, grad_scale: float = 1.0):
         self.t += 1
         ops.bump_weights_epoch(self.fp.flat)
+        ema = self.ema
+        if ema is not None:
+            ops.bump_weights_epoch(ema.fp.flat)         # the shadow's host-side weight caches are stale as well
         if self.capturable:
-            ops.adam_step_dev(self.fp.flat, self.fp.grad, self.m, self.v, self.dev_state, self.lr, self.betas[0], self.betas[1], self.eps, grad_scale,
-                              zero_grad=self.zero_grad_in_step)
+            if ema is None:
+                ops.adam_step_dev(self.fp.flat, self.fp.grad, self.m, self.v, self.dev_state, self.lr, self.betas[0], self.betas[1], self.eps, grad_scale,
+                                  zero_grad=self.zero_grad_in_step)
+            else:
+                ops.adam_ema_step_dev(self.fp.flat, self.fp.grad, self.m, self.v, ema.fp.flat, self.dev_state, self.lr, self.betas[0], self.betas[1],
+                                      self.eps, grad_scale, zero_grad=self.zero_grad_in_step, ema_rate=ema.rate, ema_warmup=ema.warmup)
             self._grad_clean = self.zero_grad_in_step
-        else:
+        elif ema is None:
             ops.adam_step(self.fp.flat, self.fp.grad, self.m, self.v, self.t, self.lr, self.betas[0], self.betas[1], self.eps, grad_scale)
+        else:
+            ops.adam_ema_step(self.fp.flat, self.fp.grad, self.m, self.v, ema.fp.flat, self.t, self.lr, self.betas[0], self.betas[1], self.eps,
+                              grad_scale, ema_rate=ema.rate, ema_warmup=ema.warmup)
 
     def set_lr(self, lr: float) -> None:
         """Change the learning rate (lr schedules).  In capturable mode the captured kernels keep the lr they were recorded with;
@@ -143,3 +169,102 @@ class StepLR:
 
     def get_last_lr(self):
         return [self.opt.get_lr()]
+
+    def state_dict(self):
+        return {"step_size": self.step_size, "gamma": self.gamma, "base_lr": self.base_lr, "last_epoch": self.last_epoch}
+
+    def load_state_dict(self, sd) -> None:
+        """Restores the schedule's position and sets the optimiser's lr to the one it prescribes there (what Adam.load_state_dict
+        restored, for a pair saved together)."""
+        self.step_size, self.gamma = int(sd["step_size"]), float(sd["gamma"])
+        self.base_lr, self.last_epoch = float(sd["base_lr"]), int(sd["last_epoch"])
+        self.opt.set_lr(self.base_lr * self.gamma ** (self.last_epoch // self.step_size))
+
+
+# per-module host-side caches (kNN graphs of the sphere prior, EdgeConv1's twin-forward output, pending BatchNorm counts, the flat
+# layout, a communicator): never copied into a shadow -- it derives its own
+_MODULE_CACHES = ("_spgan_flat", "_ec1_twin", "_sphere_graph", "_sphere_graphs", "_graph2_queue", "_pair_idx", "_bn_pending", "_comm")
+
+
+class EMA:
+    """Exponential moving average of a module's parameters (the generator EMA of Common/network_utils.py:97-108; the reference
+    declares --ema / --ema_rate, Generation/config.py:112,125).
+
+    `module` is flattened (flatten_module); `EMA.module` is a deep copy of it whose parameters live in a flat buffer with the SAME
+    offsets (asserted), so one launch averages the whole network: e <- a*e + (1-a)*p with a = min(1 - 1/t, rate) when `warmup`
+    (exp_mov_avg with global_step = t-1: the first update copies p), else a = rate (accumulate).  The shadow parameters do not
+    require gradients; `EMA.module` is an ordinary module (eval, interpolate, metrics, state_dict).
+
+    update() is the standalone update (ops.ema_update_dev, its own device-side step counter: capturable) for callers with their own
+    optimiser; Adam.attach_ema(ema) instead folds the update into that optimiser's step (t = its step count).
+
+    Buffers are not averaged (accumulate averages parameters only): copy_buffers() copies the source's BatchNorm running statistics
+    and counts into the shadow -- the StyleGAN convention; call it before using the shadow in eval mode and before its state_dict().
+    This deliberately differs from the reference helpers applied to a deep-copied G, whose buffers would stay frozen at the copy."""
+
+    def __init__(self, module: nn.Module, rate: float = 0.999, warmup: bool = True):
+        if not 0.0 <= float(rate) <= 1.0:
+            raise ValueError("EMA rate must lie in [0, 1], got %r" % (rate,))
+        self.src = flatten_module(module)
+        memo = {}
+        for m in module.modules():
+            for k in _MODULE_CACHES:
+                if k in m.__dict__:
+                    memo[id(m.__dict__[k])] = None              # deepcopy returns None for these; removed from the copy below
+        shadow = copy.deepcopy(module, memo)
+        for m in shadow.modules():
+            for k in _MODULE_CACHES:
+                m.__dict__.pop(k, None)
+        for p in shadow.parameters():
+            p.requires_grad_(False)
+        self.fp = flatten_module(shadow)
+        assert self.fp.offsets == self.src.offsets and self.fp.numel == self.src.numel, "EMA shadow: flat layout differs from the source's"
+        self.source, self.module = module, shadow
+        self.rate, self.warmup = float(rate), bool(warmup)
+        self._t = 0
+        self.counter = torch.zeros(1, dtype=torch.int32, device=self.fp.flat.device)     # update()'s device-side step count
+        self._opt: Optional[Adam] = None
+
+    @property
+    def t(self) -> int:
+        """Updates applied so far (the warm-up position): the attached optimiser's step count, else update()'s own."""
+        return self._opt.t if self._opt is not None else self._t
+
+    def update(self) -> None:
+        """One EMA update from the source's current parameters (two launches: counter advance + update).  Inside a captured graph
+        the host-side bookkeeping happens once, at capture: after each replay call mark_updated()."""
+        if self._opt is not None:
+            raise RuntimeError("EMA.update: this EMA is attached to an optimiser, whose step() updates it")
+        if flatten_module(self.source) is not self.src:
+            raise RuntimeError("EMA.update: the source module's parameters were re-flattened since the EMA was built")
+        self.mark_updated()
+        ops.ema_update_dev(self.fp.flat, self.src.flat, self.counter, self.rate, self.warmup)
+
+    def mark_updated(self) -> None:
+        """Host-side bookkeeping of one standalone update: the step count and the shadow's weight caches (ops.bump_weights_epoch)."""
+        self._t += 1
+        ops.bump_weights_epoch(self.fp.flat)
+
+    def copy_buffers(self) -> None:
+        """Shadow buffers (BatchNorm running statistics, num_batches_tracked) := the source's, pending counts flushed first."""
+        if hasattr(self.source, "flush_bn_counts"):
+            self.source.flush_bn_counts()
+        if hasattr(self.module, "flush_bn_counts"):
+            self.module.flush_bn_counts()
+        with torch.no_grad():
+            for (n, b), (n2, b2) in zip(self.source.named_buffers(), self.module.named_buffers()):
+                assert n == n2, (n, n2)
+                b2.copy_(b)
+
+    def state_dict(self):
+        """Shadow parameters and buffers (module state_dict, tensors cloned), rate, warm-up flag and step count."""
+        return {"module": {k: v.detach().clone() for k, v in self.module.state_dict().items()}, "rate": self.rate, "warmup": self.warmup,
+                "t": self.t}
+
+    def load_state_dict(self, sd) -> None:
+        """Copies into the existing shadow tensors (a captured graph that updates them stays valid)."""
+        self.module.load_state_dict(sd["module"])
+        self.rate, self.warmup = float(sd["rate"]), bool(sd["warmup"])
+        self._t = int(sd["t"])
+        self.counter.fill_(self._t)
+        ops.bump_weights_epoch(self.fp.flat)

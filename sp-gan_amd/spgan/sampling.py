@@ -36,6 +36,13 @@ class InputSampler:
         self.ball: Optional[torch.Tensor] = None          # [np,3] normalised template
         self.ball_order: Optional[torch.Tensor] = None    # lazily: argsort of the reference's ball_dist rows
 
+    def get_state(self) -> dict:
+        """RNG position of the sampler (resume); the cached ball order is derived data and is rebuilt on demand."""
+        return {"gen": self.gen.get_state()}
+
+    def set_state(self, state: dict) -> None:
+        self.gen.set_state(state["gen"])
+
     # ------------------------------------------------------------------ sphere prior
     def _load_ball(self):
         if self.ball is None:

@@ -13,6 +13,10 @@ a hipGraph and replayed.  The Python/launch cost of a step (~14 ms, as long as t
 inputs are copied into static buffers every step; only the sphere prior x is adopted without a copy while the caller keeps
 passing the same unmodified tensor object.  x must be constant in graph mode: the capture depends on its kNN graph, so a changed
 x costs an eager step and a re-capture (and after a few changes the harness stays eager).
+
+`ema_rate`: a generator EMA (spgan.optim.EMA, exposed as `G_ema`) advanced inside G's Adam launch -- same launch count, same graph.
+state_dict() / load_state_dict() carry everything a resumed run needs from the step (networks, optimisers, EMA); a load copies into
+the existing tensors, so a captured graph keeps replaying.
 """
 from __future__ import annotations
 
@@ -25,7 +29,7 @@ import torch.nn as nn
 from . import ops
 from .functions import DeliverySink, fused_grad_accumulation
 from .losses import GradientPenalty, dis_loss_with_grads, gen_loss_with_grads
-from .optim import Adam
+from .optim import EMA, Adam
 from .parallel import DataParallel
 
 
@@ -39,7 +43,7 @@ class TrainStep:
     def __init__(self, G: nn.Module, D: nn.Module, gan: str = "ls", use_gp: bool = False, lambda_gp: float = 10.0,
                  lr_g: float = 1e-4, lr_d: float = 1e-4, betas=(0.5, 0.99), flip_d: bool = False, flip_g: bool = False,
                  distributed: bool = False, process_group=None, graph: bool = False, graph_warmup: int = 3,
-                 reference_schedule: bool = False):
+                 reference_schedule: bool = False, ema_rate: Optional[float] = None, ema_warmup: bool = True):
         self.G, self.D = G, D
         self.gan, self.use_gp = gan, use_gp
         self.flip_d, self.flip_g = flip_d, flip_g
@@ -50,6 +54,12 @@ class TrainStep:
             self.dpG.sync_params(); self.dpD.sync_params()
         self.optG = Adam(G, lr_g, betas, capturable=graph, zero_grad_in_step=True)
         self.optD = Adam(D, lr_d, betas, capturable=graph, zero_grad_in_step=True)
+        # generator EMA: built from G's (synchronised) parameters; G's Adam launch updates it (data parallel: every rank averages its own,
+        # identical, parameters -- no communication)
+        self.ema = None
+        if ema_rate is not None:
+            self.ema = EMA(G, ema_rate, ema_warmup)
+            self.optG.attach_ema(self.ema)
         G.train(); D.train()
         # reference_schedule=True evaluates exactly the calls of model.py:239-279, including the two pieces of work this harness
         # otherwise removes because they are provably redundant: EdgeConv1 on every copy of the tiled sphere prior
@@ -245,6 +255,8 @@ class TrainStep:
             self.dpG.allreduce_grads()
             g3.replay()
         ops.bump_weights_epoch(self.optD.fp.flat); ops.bump_weights_epoch(self.optG.fp.flat)   # both networks were updated by the replayed Adam kernels: host-side weight caches are stale
+        if self.ema is not None:
+            ops.bump_weights_epoch(self.ema.fp.flat)                                             # ... and so was the EMA shadow
         for m, d in zip(self._bn_modules(), self._bn_delta):
             store = m.__dict__.setdefault("_bn_pending", {})
             for pre, pend in d.items():
@@ -253,6 +265,48 @@ class TrainStep:
                     tgt[k] = tgt.get(k, 0) + n
         self.optG.t += 1; self.optD.t += 1
         return self._static_info
+
+    @property
+    def G_ema(self) -> Optional[nn.Module]:
+        """The EMA generator (TrainStep(ema_rate=...)), else None.  Its BatchNorm buffers are G's after `ema.copy_buffers()`."""
+        return None if self.ema is None else self.ema.module
+
+    def state_dict(self) -> Dict[str, object]:
+        """Everything of the step a resumed run needs, as a snapshot (tensors cloned): G and D (parameters, BatchNorm buffers with their
+        pending counts flushed), both Adams (m, v, t, lr) and the EMA (shadow, rate, warm-up flag, t)."""
+        def snap(d):
+            return {k: (snap(v) if isinstance(v, dict) else v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in d.items()}
+        sd = {"G": snap(self.G.state_dict()), "D": snap(self.D.state_dict()), "optG": snap(self.optG.state_dict()),
+              "optD": snap(self.optD.state_dict())}
+        if self.ema is not None:
+            sd["ema"] = self.ema.state_dict()
+        return sd
+
+    def _launch_constants(self):
+        """Host values the captured Adam launches hold as kernel arguments (the lr is not one of them: it enters through the
+        device-side multiplier)."""
+        ema = None if self.ema is None else (self.ema.rate, self.ema.warmup)
+        return (tuple(self.optG.betas), self.optG.eps, tuple(self.optD.betas), self.optD.eps, ema)
+
+    def load_state_dict(self, sd) -> None:
+        """Inverse of state_dict().  Every value is copied into the tensors the step already owns (flat parameter buffers, moments, the
+        device-side step state, the shadow): a graph captured before the load keeps replaying, now from the loaded state.  Only when the
+        checkpoint changes a value the captured launches hold as an argument (Adam's betas / eps, the EMA's rate / warm-up flag) is the
+        graph dropped; the next step captures it again."""
+        if ("ema" in sd) != (self.ema is not None):
+            raise ValueError("TrainStep.load_state_dict: the checkpoint %s an EMA, this step %s" % (
+                "has" if "ema" in sd else "has no", "has one" if self.ema is not None else "has none"))
+        before = self._launch_constants()
+        self.G.load_state_dict(sd["G"]); self.D.load_state_dict(sd["D"])
+        self.optG.load_state_dict(sd["optG"]); self.optD.load_state_dict(sd["optD"])
+        if self.ema is not None:
+            self.ema.load_state_dict(sd["ema"])
+        if self._graph is not None and self._launch_constants() != before:
+            torch.cuda.synchronize()
+            self._graph = None
+            self._eager_calls = self.graph_warmup
+        ops.bump_weights_epoch(self.optG.fp.flat); ops.bump_weights_epoch(self.optD.fp.flat)
+        self.G.__dict__["_ec1_twin"] = None
 
     def step(self, x: torch.Tensor, real: torch.Tensor, z_d: torch.Tensor, z_g: torch.Tensor, alpha: Optional[torch.Tensor] = None,
              keep_grads: bool = False) -> Dict[str, torch.Tensor]:
