@@ -799,6 +799,50 @@ int spgan_mmd_cov(const float* dist, int S, int R, float* out3, float* ws, spgan
 int spgan_two_sample_knn(const float* Mxx, const float* Mxy, const float* Myy, int n0, int n1, int k, int take_sqrt, float* out9,
                          int32_t* pred, spgan_stream_t s);
 
+/* ------------------------------------------------------------------------------------------
+ * Local-shape Chamfer (Common/loss_utils.py:196-259 get_local_pair, Common/GAN_metrics.py:596-656 local_CD / pairwise_local_CD)
+ * and the GAN_metrics evaluation pieces (csrc/local_cd.hip).  Every float expression there is evaluated as written, without
+ * fma contraction; the fixed orders are listed at the top of that file.
+ * ---------------------------------------------------------------------------------------- */
+/* The K nearest points of cloud[b] ([B,N,3]) to every query[b,m] ([B,M,3]) in pointops knnquery order (ascending d^2, lower
+ * index first on equal d^2, the query itself included when it is a cloud point; metrics/pointops/src/knnquery/
+ * knnquery_cuda_kernel.cu:6-50), and their mean mu [B,M,3] and biased covariance cov [B,M,6] = [xx, xy, xz, yy, yz, zz]
+ * (compute_mean_covariance, loss_utils.py:196-205).  idx int64 [B,M,K] may be NULL.  1 <= K <= min(32, N). */
+int spgan_knn_moments(const float* query, const float* cloud, int B, int M, int N, int K, int64_t* idx, float* mu, float* cov,
+                      spgan_stream_t s);
+/* Slot gradients of the moments: gslot[b,m,k,:] = dmu[b,m]/K + (G + G^T)(cloud[b, idx[b,m,k]] - mu[b,m])/K, G the 3x3 form of
+ * dcov [B,M,6].  Summed onto the cloud points by spgan_gather_csr + spgan_scatter_slots (the query gets no gradient). */
+int spgan_moments_bwd(const int64_t* idx, const float* cloud, const float* mu, const float* dmu, const float* dcov, int B, int M, int N,
+                      int K, float* gslot, spgan_stream_t s);
+/* Nearest neighbour in both directions between a [B,Na,D] and b [B,Nb,D]: dist_a[b,i] = min_j d(a_i, b_j), idx_a the first j
+ * attaining it; dist_b / idx_b the other way.  D = 3 or 9: plain squared distance; D = 6: the 6-entry storage of symmetric 3x3
+ * matrices with the off-diagonal squared differences weighted by 2 (the 9-D distance of the full matrices).  idx_* may be NULL. */
+int spgan_nn_dim(const float* a, const float* b, int B, int Na, int Nb, int D, float* dist_a, int32_t* idx_a, float* dist_b,
+                 int32_t* idx_b, spgan_stream_t s);
+/* out[p*ostride] = (sum_i dist_a[p,i] + sum_j dist_b[p,j]) / div for p < P (fixed-order double sums rounded once to float) */
+int spgan_pair_sum(const float* dist_a, int na, const float* dist_b, int nb, int P, float div, float* out, int ostride, spgan_stream_t s);
+/* grad_a = d/d(a) of gscale[0] * (sum dist_a + sum dist_b) through the argmins of spgan_nn_dim (call once per side, swapping the
+ * roles; gather form, ascending order, no float atomics) */
+int spgan_chamfer_dim_bwd(const float* xa, const float* xb, int B, int Na, int Nb, int D, const int32_t* idxa, const int32_t* idxb,
+                          const float* gscale, float* grad_a, spgan_stream_t s);
+/* out [S,R,2] = the local Chamfer terms (mean, covariance) of every pair: the K-nearest moments of sample[s]'s points in sample[s]
+ * (computed once per sample) against those in ref[r], each Chamfer sum divided by N.  Pairs run in chunks inside one call.
+ * ws: spgan_pairwise_local_cd_ws_bytes(S, R, N, M) bytes. */
+size_t spgan_pairwise_local_cd_ws_bytes(int S, int R, int N, int M);
+int spgan_pairwise_local_cd(const float* sample, const float* ref, int S, int R, int N, int M, int K, float* out, void* ws, size_t ws_bytes,
+                            spgan_stream_t s);
+/* GAN_metrics.KNN (GAN_metrics.py:466-482): the vote of spgan_two_sample_knn with labels -1 (first set) / +1 (second set), a tied
+ * vote predicting +1.  out1[0] = fraction of clouds predicted correctly; pred: int32 [n0+n1] scratch (the +-1 predictions). */
+int spgan_two_sample_knn_pm(const float* Mxx, const float* Mxy, const float* Myy, int n0, int n1, int k, int take_sqrt, float* out1,
+                            int32_t* pred, spgan_stream_t s);
+/* Point counts of the JSD histogram (get_voxel_occ_dist, GAN_metrics.py:411-447): counts[(i*res+j)*res+k] += number of points with
+ * e_i <= x < e_{i+1}, e_j <= y < e_{j+1}, e_k <= z < e_{k+1}, e_i = -0.5 + i*(1/res) in float64; points outside are not counted.
+ * Accumulates into int32 [res^3] (the caller zeroes it). */
+int spgan_voxel_counts(const float* pts, long npts, int res, int32_t* counts, spgan_stream_t s);
+/* out [S,R] = sum_c (a[s,c] - b[r,c])^2, or sum_c |a[s,c] - b[r,c]| with l1, for feature rows a [S,D], b [R,D]
+ * (GAN_metrics.py:562-593 pairwise_simple) */
+int spgan_pairwise_simple(const float* a, const float* b, int S, int R, int D, int l1, float* out, spgan_stream_t s);
+
 /* Approximate earth mover's distance by a synchronous auction: the algorithm of the reference's emd module
  * (metrics/emd/emd_cuda.cu:93-236 behind metrics/CD_EMD/emd_/emd_module.py:33-75: `emd.forward(xyz1, xyz2, dist, assignment, price,
  * assignment_inv, bid, bid_increments, max_increments, ..., eps, iters)`), with the scratch arrays folded into one workspace and a

@@ -271,6 +271,16 @@ SIGNATURES = {
     "spgan_occupancy_counts": (I, [P, I, I, I, P, P, P]),
     "spgan_mmd_cov": (I, [P, I, I, P, P, P]),
     "spgan_two_sample_knn": (I, [P, P, P, I, I, I, I, P, P, P]),
+    "spgan_knn_moments": (I, [P, P, I, I, I, I, P, P, P, P]),
+    "spgan_moments_bwd": (I, [P, P, P, P, P, I, I, I, I, P, P]),
+    "spgan_nn_dim": (I, [P, P, I, I, I, I, P, P, P, P, P]),
+    "spgan_pair_sum": (I, [P, I, P, I, I, F, P, I, P]),
+    "spgan_chamfer_dim_bwd": (I, [P, P, I, I, I, I, P, P, P, P, P]),
+    "spgan_pairwise_local_cd_ws_bytes": (SZ, [I, I, I, I]),
+    "spgan_pairwise_local_cd": (I, [P, P, I, I, I, I, I, P, P, SZ, P]),
+    "spgan_two_sample_knn_pm": (I, [P, P, P, I, I, I, I, P, P, P]),
+    "spgan_voxel_counts": (I, [P, C.c_long, I, P, P]),
+    "spgan_pairwise_simple": (I, [P, P, I, I, I, I, P, P]),
     "spgan_stamp_begin": (I, [P, P]),
     "spgan_stamp_end": (I, [P, P, P]),
     "spgan_wall_clock_khz": (I, []),

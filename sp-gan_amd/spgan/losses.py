@@ -2,6 +2,8 @@
 
   dis_loss / gen_loss : Common/loss_utils.py:854-972 / 727-802  -> (loss, info-dict)
   GradientPenalty     : Common/gradient_penalty.py:4-37         -> callable(netD, real, fake)
+  get_local_pair      : Common/loss_utils.py:208-257            -> (like_mu12, like_var12), the shape-preserving loss
+                        (spgan/local_cd.py; not part of the train step, as in the reference's loop)
 
 Value and logit-gradients come from one HIP launch (spgan_gan_loss); the penalty's norm,
 value and gradient are HIP kernels as well.  Unlike the reference, nothing here forces a
@@ -16,6 +18,7 @@ from torch.autograd import Function
 
 from . import ops
 from .functions import input_grad_only
+from .local_cd import get_local_pair  # noqa: F401
 
 
 class _GanLossFn(Function):

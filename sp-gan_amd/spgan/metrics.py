@@ -8,6 +8,9 @@
   unit_cube_grid_point_cloud, entropy_of_occupancy_grid,     the JSD metric, metrics/evaluation_metrics.py:210-322
   jensen_shannon_divergence, jsd_between_point_cloud_sets
 
+  knn_moments, ChamferLoss,              the local-shape Chamfer of Common/loss_utils.py:94-259 and Common/GAN_metrics.py:596-656
+  local_CD, pairwise_local_cd            (spgan/local_cd.py over csrc/local_cd.hip); the GAN_metrics drivers are spgan/gan_metrics.py
+
   emdFunction / emdModule                the auction EMD of metrics/CD_EMD/emd_/emd_module.py:33-85 (over emd_cuda.cu)
   emd_approx, pairwise_emd, EMD_CD,      the EMD half of metrics/evaluation_metrics.py:26-35,52-126,176-207.  There `emd_approx`
   compute_all_metrics                    calls StructuralLosses.match_cost, an extension that is NOT part of the reference tree;
@@ -28,6 +31,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib
+from .local_cd import ChamferLoss, knn_moments, local_CD, pairwise_local_cd  # noqa: F401
 from .ops import _f32, _p, _s, check
 
 Tensor = torch.Tensor
