@@ -28,6 +28,7 @@
 #include "gemm_wide.hpp"
 #include "gemm_tn_wide3.hpp"
 #include "sparse_rows.hpp"
+#include "split_bf16.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -125,16 +126,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int LDX3 = 52;  // LDS row: three planes of 32 bf16 (16 words each) + 4 words of padding; 52 = 4*13 keeps the 16-byte
                           // fragment reads of 16 consecutive rows on disjoint 4-bank groups (conflict-free ds_read_b128)
 
-__device__ __forceinline__ void st_row4b3(float* p, float4 v) {  // p: word address of this k-quad inside the hi plane
-  f32x4v f = {v.x, v.y, v.z, v.w};
-  const bf16x4 hi = __builtin_convertvector(f, bf16x4);
-  const f32x4v r1 = f - __builtin_convertvector(hi, f32x4v);
-  const bf16x4 mid = __builtin_convertvector(r1, bf16x4);
-  const f32x4v r2 = r1 - __builtin_convertvector(mid, f32x4v);
-  const bf16x4 lo = __builtin_convertvector(r2, bf16x4);
-  *reinterpret_cast<bf16x4*>(p) = hi;
-  *reinterpret_cast<bf16x4*>(p + 16) = mid;
-  *reinterpret_cast<bf16x4*>(p + 32) = lo;
+__device__ __forceinline__ void st_row4b3(float* p, float4 v) {  // p: word address of this k-quad inside the hi plane (split_bf16.hpp's split)
+  st_split4(reinterpret_cast<uint32_t*>(p), 16, v);
 }
 
 __device__ __forceinline__ void st_row4(float* p, float4 v) {  // rows are 8-byte aligned (LDT even)

@@ -295,7 +295,8 @@ bool spgan_nt_wide16_selected(const spgan_gemm_nt_args& a) {
   static const bool off = getenv("SPGAN_NT_WIDE16") && atoi(getenv("SPGAN_NT_WIDE16")) == 0;
   if (off || a.tile_hint == 1 || !spgan_nt_wide16_eligible(a)) return false;
   if (a.tile_hint == 2) return true;
-  return (long)(a.M / 256) * (a.N / 256) >= 256 && a.K >= 128;   // as spgan_nt_wide_pays: the tiles fill the chip, a k-loop worth its ramp
+  // tiles of ONE group (as spgan_nt_wide_pays): a grouped launch must pick the kernel, and so the summation order, of its separate passes
+  return (long)((a.p_group_rows > 0 ? a.p_group_rows : a.M) / 256) * (a.N / 256) >= 256 && a.K >= 128;   // the tiles fill the chip, a k-loop worth its ramp
 }
 
 int spgan_launch_nt_wide16(const spgan_gemm_nt_args& a, hipStream_t s) {

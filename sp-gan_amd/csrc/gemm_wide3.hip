@@ -411,8 +411,9 @@ bool spgan_nt_wide3_selected(const spgan_gemm_nt_args& a) {
   static const bool off = getenv("SPGAN_NT_WIDE3") && atoi(getenv("SPGAN_NT_WIDE3")) == 0;
   if (off || a.tile_hint == 1 || !spgan_nt_wide3_eligible(a)) return false;
   if (a.tile_hint == 2) return true;
-  // a workgroup per CU at least, and a k-loop worth its ramp (the 128-row split kernel serves the rest)
-  return (long)(a.M / 256) * (a.N / 128) >= 128 && a.K >= 64;
+  // a workgroup per CU at least, and a k-loop worth its ramp (the 128-row split kernel serves the rest); tiles of ONE group, as in
+  // spgan_nt_wide3_config: a grouped launch must pick the kernel, and so the summation order, of its separate passes
+  return (long)((a.p_group_rows > 0 ? a.p_group_rows : a.M) / 256) * (a.N / 128) >= 128 && a.K >= 64;
 }
 
 int spgan_launch_nt_wide3(const spgan_gemm_nt_args& a, hipStream_t s) {

@@ -293,7 +293,8 @@ def d_forward_groups(P: Dict[str, Tensor], bufs: Optional[Dict[str, Tensor]], xs
     """The conv stacks of several train-mode passes D(x_0), D(x_1), ... as ONE batch: every layer is a single GEMM over the rows of all
     passes (ops.gemm_bn_groups), every pass keeps its own BatchNorm batch statistics, and the running statistics (and call counts)
     advance pass after pass in list order -- the activations, statistics and buffers are those of separate d_forward(head=False) calls
-    bit for bit (tests/test_kernels2_gpu.py::test_gemm_bn_groups, test_parity_gpu.py::test_discriminator_grouped_forward...).
+    bit for bit, in every operand mode (tests/test_operand_modes_gpu.py::test_gemm_bn_groups_equal_separate_calls and
+    ::test_discriminator_grouped_passes_equal_separate_calls, tests/test_parity_gpu.py::test_discriminator_grouped_passes_equal_separate_calls).
     Returns [(pooled_g [B,C4], ctx_g)]: the contexts are VIEWS of the batched tensors, laid out exactly like d_forward's, so d_backward /
     d_double_backward run per pass unchanged.  Needs equal shapes and N % 128 == 0."""
     G = len(xs_cm)

@@ -883,16 +883,29 @@ def multi_addn(dsts, srcs_per_dst):
             d.add_(s.reshape(d.shape))
 
 
+BF16_MAX = float.fromhex("0x1.fep127")       # the largest finite bfloat16
+
+
+def _split_bf16x3(x):
+    """The split-bf16 planes of fp32 x (csrc/split_bf16.hpp): (hi, mid, lo) bfloat16 with hi + mid + lo = x, exactly for |x| >= 2^-110 (below,
+    lo is rounded to bf16's subnormal spacing).  Finite x: hi = RN(clamp(x, +-BF16_MAX)) (no plane overflows), mid = RN(x - hi),
+    lo = RN(x - hi - mid); non-finite x: (+0, +0, x)."""
+    x = x.float()
+    fin = torch.isfinite(x)
+    xf = torch.where(fin, x, torch.zeros_like(x))
+    hi = xf.clamp(-BF16_MAX, BF16_MAX).bfloat16(); r1 = xf - hi.float()
+    mid = r1.bfloat16(); r2 = r1 - mid.float()
+    return hi, mid, torch.where(fin, r2, x).bfloat16()
+
+
 def split_image(W, out=None):
-    """ops.split_image: the split-bf16 image of W [N,K] (spgan_split_bf16x3_image): hi + mid + lo = W exactly (round to nearest at each level),
+    """ops.split_image: the split-bf16 image of W [N,K] (spgan_split_bf16x3_image): the planes of _split_bf16x3,
     laid out [K/16][plane][N][16 bf16], the two 16-byte halves of a row swapped where bit 3 of n is set, rows with bit 5 of n set negated."""
     N, K = W.shape
     assert N % 128 == 0 and K % 16 == 0
     n = torch.arange(N, device=W.device)
     W = torch.where(((n >> 5) & 1).bool()[:, None], -W, W)                           # negated BEFORE the split, like the kernel (an exact-zero residual keeps +0)
-    hi = W.bfloat16(); r1 = W - hi.float()
-    mid = r1.bfloat16(); r2 = r1 - mid.float()
-    planes = torch.stack([hi, mid, r2.bfloat16()])                                   # [3, N, K]
+    planes = torch.stack(_split_bf16x3(W))                                            # [3, N, K]
     img = planes.view(3, N, K // 16, 2, 8).permute(2, 0, 1, 3, 4)                    # [K/16, 3, N, 2, 8]
     img = torch.where(((n >> 3) & 1).bool()[None, None, :, None, None], img.flip(3), img).contiguous()
     res = img.view(torch.uint8).reshape(-1)

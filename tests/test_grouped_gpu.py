@@ -218,8 +218,8 @@ def _d_setup(B, N, salt):
     return nets, P, xs
 
 
-@pytest.mark.parametrize("mode", ["f32", "f16"])
-@pytest.mark.parametrize("B,N,with_dbl", [(8, 2048, True), (32, 2048, True), (16, 1024, False)])
+@pytest.mark.parametrize("mode", ["f32", "f16", "bf16x3"])
+@pytest.mark.parametrize("B,N,with_dbl", [(8, 2048, True), (32, 2048, True), (16, 1024, False), (16, 2048, True), (4, 2048, True)])
 def test_d_backward_joint_equals_separate_calls(ops, B, N, with_dbl, mode):
     """nets.d_backward_joint (the real pass, the fake pass and the penalty's double backward in lock step, every layer's launch issued once) gives,
     per pass, the gradients of nets.d_backward / nets.d_double_backward bit for bit.  mode "f16": no fused layer-backward kernel -- the joint node

@@ -633,7 +633,12 @@ def test_discriminator_grouped_passes_equal_separate_calls(sp):
     """Discriminator.forward_stacks_grouped (the D step's D(real), D(fake), D(x_hat) conv stacks as one batch) and
     forward_stack_after_stats_pass (the G step's statistics pass + D(G(z))): logits, every gradient and all BatchNorm buffers are those
     of the separate calls, bit for bit."""
-    B, N = 4, 256
+    grouped_passes_equal_separate_calls(sp, 4, 256)
+
+
+def grouped_passes_equal_separate_calls(sp, B, N):
+    """The body of test_discriminator_grouped_passes_equal_separate_calls at batch B, N points (tests/test_operand_modes_gpu.py runs it at
+    the shapes where a grouped layer's total row count and one pass's rows fall on different sides of a kernel-selection threshold)."""
     params = fr.init_params(orc.discriminator_shapes(), salt=11)
     xs = [(fr.synthetic_real(B, N, seed=90 + i) * (1.0 + 0.2 * i)).transpose(2, 1).contiguous().cuda() for i in range(3)]
     seeds = [fr.normal("grp.seed%d" % i, (B, 1)).cuda() for i in range(3)]
