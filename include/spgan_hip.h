@@ -627,6 +627,31 @@ int spgan_scatter_slots(const float* dout, int ld, int col0, int C, const int32_
 int spgan_group_center_bwd(const float* dout, int ld, int Q, int K, int C, float* dcenter, spgan_stream_t s);
 int spgan_edge_features_cm_bwd(const float* dE, const int32_t* rowptr, const int32_t* src, int B, int C, int N, int k, float* dx,
                                spgan_stream_t s);
+/* PointNet++ set abstraction / feature propagation (Common/pointnet_util.py:146-320; the extension ops of metrics/pointnet2_ops).
+ *   spgan_three_nn:              idx int64 [B,N,k], weight [B,N,k], k = min(3,S): the k nearest centres xyz2 [B,S,3] of every point xyz1 [B,N,3]
+ *                                (ascending distance, lower index first on exact ties) and w = (1/(d+1e-8)) / sum(1/(d+1e-8)); d in
+ *                                spgan_square_distance's arithmetic; no [B,N,S] matrix, no workspace          pointnet_util.py:301-307
+ *   spgan_three_interpolate:     out[(b*N+n)*ld_out + col0 + c] = sum_j weight[b,n,j]*points2[b,idx[b,n,j],c], points2 [B,S,D]; the slice
+ *                                [col0, col0+D) of a wider row buffer takes the place of the torch.cat of :312; *bad |= 1 on an index
+ *                                outside [0,S) (bad may be NULL; such a slot contributes 0)                   pointnet_util.py:308
+ *   spgan_three_interpolate_bwd: dpoints2[m,c] = sum_{e in slots(m)} weight[e]*dout[(e/k)*ld + col0 + c] over spgan_gather_csr's slot
+ *                                lists of idx [B, N*k] (deterministic; the weights carry no gradient, as three_nn in pointnet2_ops)
+ *   spgan_group_max:             pooled[q,c] = max_{j<K} lrelu(y[(q*K+j)*ld + c]*scale[c] + shift[c], slope), argmax int32 = that global row
+ *                                (first maximum); scale/shift may both be NULL                                pointnet_util.py:203-205, 261-262
+ *   spgan_group_max_bwd:         g [Q*K,C] = gpool*lrelu'(pooled) at the arg-max row, 0 elsewhere; gstat [Q,2C] = [that value | value*xhat(y)]
+ *                                (its column sums are the BatchNorm backward's sums); argmax NULL with K = 1: every row its own group
+ *   spgan_cm_to_rows / spgan_rows_to_cm: x [B,C,N] <-> columns [col0, col0+C) of a [B*N, ld] row buffer    pointnet_util.py:190-192, 311-316 */
+int spgan_three_nn(const float* xyz1, const float* xyz2, int B, int N, int S, int64_t* idx, float* weight, spgan_stream_t s);
+int spgan_three_interpolate(const float* points2, const int64_t* idx, const float* weight, int B, int N, int S, int D, int k, float* out,
+                            int ld_out, int col0, int32_t* bad, spgan_stream_t s);
+int spgan_three_interpolate_bwd(const float* dout, int ld, int col0, int D, const float* weight, int k, const int32_t* rowptr,
+                                const int32_t* src, int BS, float* dpoints2, spgan_stream_t s);
+int spgan_group_max(const float* y, int ld, int Q, int K, int C, const float* scale, const float* shift, float slope, float* pooled,
+                    int32_t* argmax, spgan_stream_t s);
+int spgan_group_max_bwd(const float* gpool, const float* pooled, const int32_t* argmax, const float* y, int ld, const float* mean,
+                        const float* invstd, float slope, int Q, int K, int C, float* g, float* gstat, spgan_stream_t s);
+int spgan_cm_to_rows(const float* x_cm, int B, int C, int N, float* rows, int ld, int col0, spgan_stream_t s);
+int spgan_rows_to_cm(const float* rows, int ld, int col0, int B, int C, int N, float* x_cm, spgan_stream_t s);
 /* Per-channel scalar algebra of the double backward, one launch each:
  *   coeffs out4C = [dgammaA | sbarA | xsum0 | xsum1];  phaseb: sums2C = [xsum0+gamma*s0 | xsum1+gamma*s1+invstd*sbarA], dgamma = dgammaA+s1 */
 int spgan_bn_dbl_coeffs(const float* U0, const float* U1, const float* Ugz, const float* S0, const float* S1, const float* gamma,

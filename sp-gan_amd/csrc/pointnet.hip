@@ -4,23 +4,9 @@
 // one thread per query streaming the candidate set through LDS tiles (as spgan_knn), no N x M matrix unless the
 // caller asks for it (square_distance).
 #include "common.hpp"
+#include "pointnet_dist.hpp"
 
 namespace {
-
-// ((-2*<a,b>) + |a|^2) + |b|^2 in fp32, products and sums rounded separately like torch's matmul/sum on 3-vectors.
-template <int C>
-__device__ __forceinline__ float sqdist_expanded(const float (&a)[C], float an, const float* __restrict__ b, float bn) {
-  float dot = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) dot = fmaf(a[c], b[c], dot);
-  return (-2.f * dot + an) + bn;
-}
-
-__device__ __forceinline__ float norm2(const float* __restrict__ p, int C) {
-  float s = 0.f;
-  for (int c = 0; c < C; ++c) s = fmaf(p[c], p[c], s);
-  return s;
-}
 
 // dist[b,n,m] = square_distance(src[b,n], dst[b,m])      Common/pointnet_util.py:19-40
 __global__ void square_distance_kernel(const float* __restrict__ src, const float* __restrict__ dst, int N, int M, int C, float* __restrict__ out) {

@@ -1,0 +1,19 @@
+// The reference's square_distance arithmetic (Common/pointnet_util.py:19-40), shared by every kernel that must land on the same
+// float32 value as its `-2ab + |a|^2 + |b|^2` form (golden G9): ball query, kNN, three_nn.
+#pragma once
+#include "common.hpp"
+
+// ((-2*<a,b>) + |a|^2) + |b|^2 in fp32, products and sums rounded separately like torch's matmul/sum on 3-vectors.
+template <int C>
+__device__ __forceinline__ float sqdist_expanded(const float (&a)[C], float an, const float* __restrict__ b, float bn) {
+  float dot = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) dot = fmaf(a[c], b[c], dot);
+  return (-2.f * dot + an) + bn;
+}
+
+__device__ __forceinline__ float norm2(const float* __restrict__ p, int C) {
+  float s = 0.f;
+  for (int c = 0; c < C; ++c) s = fmaf(p[c], p[c], s);
+  return s;
+}

@@ -265,6 +265,13 @@ SIGNATURES = {
     "spgan_scatter_slots": (I, [P, I, I, I, P, P, I, P, P]),
     "spgan_group_center_bwd": (I, [P, I, I, I, I, P, P]),
     "spgan_edge_features_cm_bwd": (I, [P, P, P, I, I, I, I, P, P]),
+    "spgan_three_nn": (I, [P, P, I, I, I, P, P, P]),
+    "spgan_three_interpolate": (I, [P, P, P, I, I, I, I, I, P, I, I, P, P]),
+    "spgan_three_interpolate_bwd": (I, [P, I, I, I, P, I, P, P, I, P, P]),
+    "spgan_group_max": (I, [P, I, I, I, I, P, P, F, P, P, P]),
+    "spgan_group_max_bwd": (I, [P, P, P, P, I, P, P, F, I, I, I, P, P, P]),
+    "spgan_cm_to_rows": (I, [P, I, I, I, P, I, I, P]),
+    "spgan_rows_to_cm": (I, [P, I, I, I, I, I, P, P]),
     "spgan_nn_distance": (I, [P, P, I, I, I, P, P, P]),
     "spgan_chamfer_bwd": (I, [P, P, I, I, I, P, P, P, P, P, P]),
     "spgan_chamfer_pairs": (I, [P, P, I, I, I, I, P, P]),

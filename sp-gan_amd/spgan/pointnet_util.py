@@ -12,6 +12,15 @@ indexing (pointnet_util.py:43-60, pointconv_util.py:174-197), with a determinist
     knn_point(nsample, xyz, new_xyz)                   -> int64 [B,S,nsample]  (ascending; the reference's order is unspecified)
     group(nsample, xyz, points)                        -> (new_points [B,N,K,C+D], grouped_xyz_norm [B,N,K,C])
     sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, start=None)
+
+PointNet++ modules (Common/pointnet_util.py:146-320; inputs / outputs channel-major [B,C,N] as there):
+
+    sample_and_group_all(xyz, points)                  -> (zeros [B,1,3], [B,1,N,3+D])
+    three_nn(xyz1, xyz2)                               -> (idx int64 [B,N,k], weight [B,N,k]), k = min(3,S); no gradient
+    three_interpolate(points2, idx, weight)            [B,S,D] -> [B,N,D]; gradient to points2 only
+    PointNetSetAbstraction(npoint, radius, nsample, in_channel, mlp, group_all)
+    PointNetSetAbstractionMsg(npoint, radius_list, nsample_list, in_channel, mlp_list)
+    PointNetFeaturePropagation(in_channel, mlp)
 """
 from __future__ import annotations
 
@@ -193,3 +202,383 @@ def sample_and_group(npoint: int, radius: float, nsample: int, xyz: Tensor, poin
     if returnfps:
         return new_xyz, new_points, index_points(xyz, idx), fps_idx
     return new_xyz, new_points
+
+
+# =============================================================================================
+# PointNet++ set abstraction / feature propagation (Common/pointnet_util.py:146-320)
+# =============================================================================================
+# The modules below are the reference's: same constructor arguments, attribute names (mlp_convs / mlp_bns, conv_blocks.i.j / bn_blocks.i.j)
+# and creation order, so the same seed gives the same initial parameters and a reference state_dict loads with strict=True.  The
+# nn.Conv / nn.BatchNorm children are parameter containers only -- their forward is never called; the arithmetic is HIP:
+#   rows [B*S*K, 3+D] (spgan_group_concat) -> per layer one GEMM whose epilogue yields the BatchNorm batch statistics, the previous
+#   layer's BatchNorm + ReLU applied on the operand load (ops.gemm_nt, slope 0) -> spgan_group_max (BatchNorm + ReLU + max over K).
+#   Backward: spgan_group_max_bwd -> ops.bn_bwd_apply / ops.gemm_tn / ops.gemm_nt_bnbwd per layer, as the Discriminator's generic path.
+RELU = 0.0     # slope of the (leaky-)ReLU operand modes: F.relu (pointnet_util.py:203, 261, 319)
+GROUP_MAX_K = 128     # spgan_group_max walks the K rows of a centre in one thread; longer groups (group_all: K = N) use ops.maxpool's row-parallel kernel
+
+
+def sample_and_group_all(xyz: Tensor, points: Optional[Tensor]):
+    """One group of all N points around the origin (pointnet_util.py:146-163): -> (new_xyz zeros [B,1,3], new_points [B,1,N,3+D])."""
+    xyz = _xyz(xyz, "xyz")
+    B, N, C = xyz.shape
+    new_xyz = torch.zeros((B, 1, C), dtype=torch.float32, device=xyz.device)
+    idx = torch.arange(N, dtype=torch.int64, device=xyz.device).view(1, 1, N).expand(B, 1, N).contiguous()
+    return new_xyz, _group_concat(xyz, new_xyz, None if points is None else _xyz(points, "points"), idx)
+
+
+def three_nn(xyz1: Tensor, xyz2: Tensor):
+    """The k = min(3, S) nearest centres xyz2 [B,S,3] of every point xyz1 [B,N,3] (ascending) and their normalised inverse-distance
+    weights (pointnet_util.py:301-307) -> (idx int64 [B,N,k], weight float32 [B,N,k]).  No gradient (three_nn of metrics/pointnet2_ops)."""
+    xyz1, xyz2 = _xyz(xyz1.detach(), "xyz1"), _xyz(xyz2.detach(), "xyz2")
+    B, N, C = xyz1.shape
+    S = xyz2.shape[1]
+    if C != 3 or xyz2.shape[2] != 3 or xyz2.shape[0] != B:
+        raise ValueError("three_nn expects xyz1 [B,N,3] and xyz2 [B,S,3]")
+    k = min(3, S)
+    idx = torch.empty((B, N, k), dtype=torch.int64, device=xyz1.device)
+    weight = torch.empty((B, N, k), dtype=torch.float32, device=xyz1.device)
+    check(_lib.load().spgan_three_nn(_p(xyz1), _p(xyz2), B, N, S, _p(idx), _p(weight), _s()), "three_nn", B=B, N=N, S=S)
+    return idx, weight
+
+
+def _three_interpolate_into(points2: Tensor, idx: Tensor, weight: Tensor, out2d: Tensor, col0: int) -> None:
+    """out2d[b*N+n, col0:col0+D] = sum_j weight[b,n,j] * points2[b, idx[b,n,j]]  (points2 [B,S,D] contiguous)."""
+    B, S, D = points2.shape
+    N, k = idx.shape[1], idx.shape[2]
+    bad = ops.index_check_flag(points2.device)
+    check(_lib.load().spgan_three_interpolate(_p(points2), _p(idx), _p(weight), B, N, S, D, k, _p(out2d), out2d.shape[1], col0,
+                                              None if bad is None else _p(bad), _s()), "three_interpolate", B=B, N=N, S=S, D=D, k=k)
+    ops.index_check_raise(bad, "three_interpolate: an index lies outside [0, %d)" % S)
+
+
+def _three_interpolate_bwd(dout2d: Tensor, col0: int, D: int, idx: Tensor, weight: Tensor, S: int) -> Tensor:
+    """-> dpoints2 [B,S,D]: per-centre slot lists (gather_csr), weighted, summed in slot order -- no float atomics."""
+    B, N, k = idx.shape
+    rowptr, src = gather_csr(idx.view(B, N * k), S)
+    out = torch.empty((B, S, D), dtype=torch.float32, device=dout2d.device)
+    check(_lib.load().spgan_three_interpolate_bwd(_p(dout2d), dout2d.shape[1], col0, D, _p(weight), k, _p(rowptr), _p(src), B * S, _p(out), _s()),
+          "three_interpolate_bwd", B=B, N=N, S=S, D=D)
+    return out
+
+
+def _idx_weight(idx: Tensor, weight: Tensor):
+    if idx.dtype != torch.int64 or not idx.is_cuda or idx.dim() != 3:
+        raise TypeError("idx must be an int64 GPU tensor [B,N,k]")
+    _f32(weight, "weight", 3)
+    if weight.shape != idx.shape or idx.shape[2] > 3:
+        raise ValueError("weight must match idx [B,N,k], k <= 3")
+    return idx.contiguous(), weight.detach().contiguous()
+
+
+class _ThreeInterpolateFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points2, idx, weight):
+        B, S, D = points2.shape
+        ctx.save_for_backward(idx, weight)
+        ctx.S = S
+        out = torch.empty((B * idx.shape[1], D), dtype=torch.float32, device=points2.device)
+        _three_interpolate_into(points2, idx, weight, out, 0)
+        return out.view(B, idx.shape[1], D)
+
+    @staticmethod
+    def backward(ctx, dout):
+        idx, weight = ctx.saved_tensors
+        D = dout.shape[2]
+        return _three_interpolate_bwd(dout.contiguous().view(-1, D), 0, D, idx, weight, ctx.S), None, None
+
+
+def three_interpolate(points2: Tensor, idx: Tensor, weight: Tensor) -> Tensor:
+    """[B,N,D] = sum_j weight[..., j] * points2[b, idx[..., j]] (pointnet_util.py:308); differentiable in points2 only."""
+    points2 = _xyz(points2, "points2")
+    idx, weight = _idx_weight(idx, weight)
+    return _ThreeInterpolateFn.apply(points2, idx, weight)
+
+
+def _cm_to_rows(x_cm: Tensor, rows: Tensor, col0: int) -> None:
+    B, C, N = x_cm.shape
+    check(_lib.load().spgan_cm_to_rows(_p(x_cm), B, C, N, _p(rows), rows.shape[1], col0, _s()), "cm_to_rows", B=B, C=C, N=N)
+
+
+def _rows_to_cm(rows: Tensor, col0: int, B: int, C: int, N: int) -> Tensor:
+    out = torch.empty((B, C, N), dtype=torch.float32, device=rows.device)
+    check(_lib.load().spgan_rows_to_cm(_p(rows), rows.shape[1], col0, B, C, N, _p(out), _s()), "rows_to_cm", B=B, C=C, N=N)
+    return out
+
+
+class _CmToRowsFn(torch.autograd.Function):
+    """[B,C,N] -> [B,N,C] (the reference's permute(0, 2, 1), materialised point-major for the kernels)."""
+
+    @staticmethod
+    def forward(ctx, x_cm):
+        B, C, N = x_cm.shape
+        rows = torch.empty((B * N, C), dtype=torch.float32, device=x_cm.device)
+        _cm_to_rows(x_cm, rows, 0)
+        return rows.view(B, N, C)
+
+    @staticmethod
+    def backward(ctx, g):
+        B, N, C = g.shape
+        return _rows_to_cm(g.contiguous().view(B * N, C), 0, B, C, N)
+
+
+class _RowsToCmFn(torch.autograd.Function):
+    """[B,N,C] -> [B,C,N]."""
+
+    @staticmethod
+    def forward(ctx, rows):
+        B, N, C = rows.shape
+        return _rows_to_cm(rows.contiguous().view(B * N, C), 0, B, C, N)
+
+    @staticmethod
+    def backward(ctx, g):
+        B, C, N = g.shape
+        rows = torch.empty((B * N, C), dtype=torch.float32, device=g.device)
+        _cm_to_rows(g.contiguous(), rows, 0)
+        return rows.view(B, N, C)
+
+
+def _cm(t: Tensor, name: str) -> Tensor:
+    _f32(t, name, 3)
+    return t.contiguous()
+
+
+def _group_max(y: Tensor, Q: int, K: int, scale: Tensor, shift: Tensor, slope: float):
+    if K > GROUP_MAX_K:
+        return ops.maxpool(y, Q, K, scale, shift, slope)
+    Cn = y.shape[1]
+    pooled = torch.empty((Q, Cn), dtype=torch.float32, device=y.device)
+    arg = torch.empty((Q, Cn), dtype=torch.int32, device=y.device)
+    check(_lib.load().spgan_group_max(_p(y), ops._ld(y), Q, K, Cn, _p(scale), _p(shift), float(slope), _p(pooled), _p(arg), _s()),
+          "group_max", Q=Q, K=K, C=Cn)
+    return pooled, arg
+
+
+def _group_max_bwd(gpool: Tensor, pooled: Tensor, argmax: Optional[Tensor], y: Tensor, mean: Tensor, invstd: Tensor, slope: float, K: int):
+    """-> (g [Q*K,C] dense gradient w.r.t. the BatchNorm output, sums [2C] = (sum g | sum g*xhat))."""
+    Q, Cn = gpool.shape
+    g = torch.empty((Q * K, Cn), dtype=torch.float32, device=gpool.device)
+    gstat = torch.empty((Q, 2 * Cn), dtype=torch.float32, device=gpool.device)
+    check(_lib.load().spgan_group_max_bwd(_p(gpool), _p(pooled), _p(argmax), _p(y), ops._ld(y), _p(mean), _p(invstd), float(slope), Q, K, Cn,
+                                          _p(g), _p(gstat), _s()), "group_max_bwd", Q=Q, K=K, C=Cn)
+    return g, ops.colsum(gstat)[0]
+
+
+class _Holder:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class _SharedMLPFn(torch.autograd.Function):
+    """rows a0 [Q*K, Cin] -> [Q, Cout]: (1x1 conv -> BatchNorm -> ReLU) per layer, then max over the K consecutive rows of a group
+    (K = 1: the per-row activations).  inputs: holder(K, training, bns = the nn.BatchNorm modules), a0, then (weight, bias, gamma, beta)
+    per layer."""
+
+    @staticmethod
+    def forward(ctx, holder, a0, *params):
+        K, training = holder.K, holder.training
+        M = a0.shape[0]
+        Q = M // K
+        ys, bns = [], []
+        a, pro = a0, None
+        for li, bn in enumerate(holder.bns):
+            W, b, gamma, beta = params[4 * li:4 * li + 4]
+            W2 = W.view(W.shape[0], W.shape[1])
+            if training:
+                y, st = ops.gemm_nt(a, W2, b, bn=(gamma, beta, bn.running_mean, bn.running_var), pro=pro)
+                bn.num_batches_tracked += 1
+            else:
+                y = ops.gemm_nt(a, W2, b, pro=pro)
+                st = ops.bn_prepare(None, None, gamma, beta, M, False, bn.running_mean, bn.running_var)
+            ys.append(y); bns.append(st)
+            a, pro = y, (st[0], st[1], RELU)
+        sc, sh = bns[-1][0], bns[-1][1]
+        if K == 1:
+            out, arg = ops.affine_act(ys[-1], sc, sh, RELU), None
+        else:
+            out, arg = _group_max(ys[-1], Q, K, sc, sh, RELU)
+        ctx.K, ctx.training, ctx.ys, ctx.bns, ctx.arg = K, training, ys, bns, arg
+        ctx.save_for_backward(a0, out, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        a0, out, *params = ctx.saved_tensors
+        K, ys, bns = ctx.K, ctx.ys, ctx.bns
+        M = a0.shape[0]
+        L = len(ys)
+        grads = [None] * len(params)
+        g, sums = _group_max_bwd(dout.contiguous(), out, ctx.arg, ys[-1], bns[-1][3], bns[-1][2], RELU, K)
+        da0 = None
+        for li in range(L - 1, -1, -1):
+            W, b, gamma, beta = [p.detach() for p in params[4 * li:4 * li + 4]]
+            W2 = W.view(W.shape[0], W.shape[1])
+            Cn = W2.shape[0]
+            sc, sh, inv, mu = bns[li]
+            grads[4 * li + 2], grads[4 * li + 3] = sums[Cn:].clone(), sums[:Cn].clone()
+            if ctx.training:
+                dy = ops.bn_bwd_apply(g, ys[li], mu, inv, gamma, sums, M)
+                grads[4 * li + 1] = torch.zeros_like(b)            # a bias in front of a train-mode BatchNorm: exactly zero gradient
+            else:
+                dy = ops.bn_bwd_apply(g, ys[li], mu, inv, gamma, torch.zeros_like(sums), M)
+                grads[4 * li + 1] = ops.colsum(dy)[0]
+            if li > 0:
+                psc, psh, pinv, pmu = bns[li - 1]
+                grads[4 * li] = ops.gemm_tn(dy, ys[li - 1], pro=(psc, psh, RELU)).view_as(W)
+                g, s0, s1 = ops.gemm_nt_bnbwd(dy, W2.t().contiguous(), ys[li - 1], psc, psh, pmu, pinv, RELU)
+                sums = torch.cat([s0, s1])
+            else:
+                grads[0] = ops.gemm_tn(dy, a0).view_as(W)
+                if ctx.needs_input_grad[1]:
+                    da0 = ops.gemm_nt(dy, W2.t().contiguous())
+        return (None, da0) + tuple(g_ if need else None for g_, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+def _mlp_params(convs, bns):
+    out = []
+    for conv, bn in zip(convs, bns):
+        out += [conv.weight, conv.bias, bn.weight, bn.bias]
+    return out
+
+
+def _shared_mlp(rows: Tensor, K: int, convs, bns, training: bool, first_weight: Optional[Tensor] = None) -> Tensor:
+    params = _mlp_params(convs, bns)
+    if first_weight is not None:
+        params[0] = first_weight
+    return _SharedMLPFn.apply(_Holder(K=K, training=training, bns=list(bns)), rows, *params)
+
+
+class PointNetSetAbstraction(torch.nn.Module):
+    """pointnet_util.py:166-207.  forward(xyz [B,3,N], points [B,D,N] | None, start=None) -> (new_xyz [B,3,S], new_points [B,mlp[-1],S]);
+    start = the FPS start indices [B] (the reference draws them with torch.randint; None does the same)."""
+
+    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all):
+        super().__init__()
+        self.npoint, self.radius, self.nsample = npoint, radius, nsample
+        self.mlp_convs = torch.nn.ModuleList()
+        self.mlp_bns = torch.nn.ModuleList()
+        last_channel = in_channel
+        for out_channel in mlp:
+            self.mlp_convs.append(torch.nn.Conv2d(last_channel, out_channel, 1))
+            self.mlp_bns.append(torch.nn.BatchNorm2d(out_channel))
+            last_channel = out_channel
+        self.group_all = group_all
+
+    def forward(self, xyz: Tensor, points: Optional[Tensor], start: Optional[Tensor] = None):
+        xyz_pm = _CmToRowsFn.apply(_cm(xyz, "xyz"))
+        pts_pm = None if points is None else _CmToRowsFn.apply(_cm(points, "points"))
+        if self.group_all:
+            new_xyz, new_points = sample_and_group_all(xyz_pm, pts_pm)
+        else:
+            new_xyz, new_points = sample_and_group(self.npoint, self.radius, self.nsample, xyz_pm, pts_pm, start=start)
+        B, S, K, Cin = new_points.shape
+        out = _shared_mlp(new_points.view(B * S * K, Cin), K, self.mlp_convs, self.mlp_bns, self.training)
+        return _RowsToCmFn.apply(new_xyz), _RowsToCmFn.apply(out.view(B, S, -1))
+
+
+class PointNetSetAbstractionMsg(torch.nn.Module):
+    """pointnet_util.py:210-267 (multi-scale grouping: one shared MLP per radius, outputs concatenated over channels)."""
+
+    def __init__(self, npoint, radius_list, nsample_list, in_channel, mlp_list):
+        super().__init__()
+        self.npoint, self.radius_list, self.nsample_list = npoint, radius_list, nsample_list
+        self.conv_blocks = torch.nn.ModuleList()
+        self.bn_blocks = torch.nn.ModuleList()
+        for i in range(len(mlp_list)):
+            convs = torch.nn.ModuleList()
+            bns = torch.nn.ModuleList()
+            last_channel = in_channel + 3
+            for out_channel in mlp_list[i]:
+                convs.append(torch.nn.Conv2d(last_channel, out_channel, 1))
+                bns.append(torch.nn.BatchNorm2d(out_channel))
+                last_channel = out_channel
+            self.conv_blocks.append(convs)
+            self.bn_blocks.append(bns)
+
+    def forward(self, xyz: Tensor, points: Optional[Tensor], start: Optional[Tensor] = None):
+        xyz_pm = _CmToRowsFn.apply(_cm(xyz, "xyz"))
+        pts_pm = None if points is None else _CmToRowsFn.apply(_cm(points, "points"))
+        B, N, C = xyz_pm.shape
+        S = self.npoint
+        fps_idx = farthest_point_sample(xyz_pm.detach(), S, start)
+        new_xyz = index_points(xyz_pm, fps_idx)
+        outs = []
+        for i, radius in enumerate(self.radius_list):
+            K = self.nsample_list[i]
+            idx = query_ball_point(radius, K, xyz_pm.detach(), new_xyz.detach())
+            rows = _group_concat(xyz_pm, new_xyz, pts_pm, idx).view(B * S * K, -1)        # [xyz - centre | features]
+            w0 = self.conv_blocks[i][0].weight
+            if pts_pm is not None:
+                # the reference concatenates [features | xyz - centre] (:253): the same product with the weight's input columns rotated
+                D = pts_pm.shape[2]
+                w0 = torch.cat([w0[:, D:], w0[:, :D]], dim=1)
+            out = _shared_mlp(rows, K, self.conv_blocks[i], self.bn_blocks[i], self.training, first_weight=w0)
+            outs.append(_RowsToCmFn.apply(out.view(B, S, -1)))
+        return _RowsToCmFn.apply(new_xyz), torch.cat(outs, dim=1)
+
+
+class _PropagateInputFn(torch.autograd.Function):
+    """rows [B*N, D1+D2] = [points1 | three_interpolate(points2)] (pointnet_util.py:298-314) written into ONE buffer (no torch.cat)."""
+
+    @staticmethod
+    def forward(ctx, points1, points2, idx, weight):
+        B, D2, S = points2.shape
+        N = idx.shape[1]
+        D1 = 0 if points1 is None else points1.shape[1]
+        rows = torch.empty((B * N, D1 + D2), dtype=torch.float32, device=points2.device)
+        if points1 is not None:
+            _cm_to_rows(points1, rows, 0)
+        p2 = torch.empty((B * S, D2), dtype=torch.float32, device=points2.device)
+        _cm_to_rows(points2, p2, 0)
+        _three_interpolate_into(p2.view(B, S, D2), idx, weight, rows, D1)
+        ctx.save_for_backward(idx, weight)
+        ctx.dims = (B, N, S, D1, D2)
+        return rows
+
+    @staticmethod
+    def backward(ctx, drows):
+        idx, weight = ctx.saved_tensors
+        B, N, S, D1, D2 = ctx.dims
+        drows = drows.contiguous()
+        d1 = d2 = None
+        if D1 and ctx.needs_input_grad[0]:
+            d1 = _rows_to_cm(drows, 0, B, D1, N)
+        if ctx.needs_input_grad[1]:
+            dp2 = _three_interpolate_bwd(drows, D1, D2, idx, weight, S)
+            d2 = _rows_to_cm(dp2.view(B * S, D2), 0, B, D2, S)
+        return d1, d2, None, None
+
+
+class PointNetFeaturePropagation(torch.nn.Module):
+    """pointnet_util.py:270-320.  forward(xyz1 [B,3,N], xyz2 [B,3,S], points1 [B,D1,N] | None, points2 [B,D2,S]) -> [B,mlp[-1],N].
+    The interpolation weights carry no gradient to xyz1 / xyz2 (three_nn is not differentiable in metrics/pointnet2_ops either)."""
+
+    def __init__(self, in_channel, mlp):
+        super().__init__()
+        self.mlp_convs = torch.nn.ModuleList()
+        self.mlp_bns = torch.nn.ModuleList()
+        last_channel = in_channel
+        for out_channel in mlp:
+            self.mlp_convs.append(torch.nn.Conv1d(last_channel, out_channel, 1))
+            self.mlp_bns.append(torch.nn.BatchNorm1d(out_channel))
+            last_channel = out_channel
+
+    def forward(self, xyz1: Tensor, xyz2: Tensor, points1: Optional[Tensor], points2: Tensor) -> Tensor:
+        if torch.is_grad_enabled() and (xyz1.requires_grad or xyz2.requires_grad):
+            raise NotImplementedError(
+                "PointNetFeaturePropagation: no gradient to xyz1 / xyz2.  The interpolation weights are produced by three_nn, which is "
+                "non-differentiable (as in metrics/pointnet2_ops); the pure-torch reference differentiates them with a 1/(d+1e-8)^2 "
+                "factor that is ~1e16 on coincident points.  Pass xyz1.detach() / xyz2.detach().")
+        xyz1, xyz2, points2 = _cm(xyz1, "xyz1"), _cm(xyz2, "xyz2"), _cm(points2, "points2")
+        if points1 is not None:
+            points1 = _cm(points1, "points1")
+        B, _, N = xyz1.shape
+        S = xyz2.shape[2]
+        if S == 1:
+            # the reference's repeat branch (:298-299): every point takes the single centre's features
+            idx = torch.zeros((B, N, 1), dtype=torch.int64, device=xyz1.device)
+            weight = torch.ones((B, N, 1), dtype=torch.float32, device=xyz1.device)
+        else:
+            idx, weight = three_nn(_CmToRowsFn.apply(xyz1), _CmToRowsFn.apply(xyz2))
+        rows = _PropagateInputFn.apply(points1, points2, idx, weight)
+        out = _shared_mlp(rows, 1, self.mlp_convs, self.mlp_bns, self.training)
+        return _RowsToCmFn.apply(out.view(B, N, -1))
