@@ -652,6 +652,30 @@ int spgan_group_max_bwd(const float* gpool, const float* pooled, const int32_t* 
                         const float* invstd, float slope, int Q, int K, int C, float* g, float* gstat, spgan_stream_t s);
 int spgan_cm_to_rows(const float* x_cm, int B, int C, int N, float* rows, int ld, int col0, spgan_stream_t s);
 int spgan_rows_to_cm(const float* rows, int ld, int col0, int B, int C, int N, float* x_cm, spgan_stream_t s);
+/* PointConv density set abstraction (Common/pointconv_util.py:199-383).  Deterministic: fixed summation orders, no float atomics.
+ *   spgan_kde_density:             density[b,i] = mean_j exp(-d_ij / (2 h^2)) / (2.5 h), d = spgan_square_distance's expanded form evaluated in
+ *                                  float64 (d_ii is a rounding residue or zero); inv_density (may be NULL) = 1/density in the same launch;
+ *                                  xyz [B,N,3]; no [B,N,N] matrix, no workspace                                   pointconv_util.py:199-209, 357
+ *   spgan_kde_density_bwd:         dxyz_i = -(1/(h^2 N 2.5h)) sum_j (G_i + G_j) w_ij (x_i - x_j), w_ij = exp(-d_ij/(2h^2)),
+ *                                  G = g - ginv * inv_density^2 (g: gradient of density, ginv: of 1/density; either may be NULL)
+ *   spgan_group_density_scale:     scale[q*K + k] = v_k / max_k v_k, v_k = inv_density[b, idx[b,s,k]], q = b*S + s; *bad |= 1 on an index
+ *                                  outside [0,N) (bad may be NULL; such a slot gets 0)                              pointconv_util.py:147, 370-371
+ *   spgan_group_density_scale_bwd: dslot[q*K + k] = g_k/m - [k == first arg-max] (sum_j g_j v_j)/m^2: the gradient per gathered slot, summed
+ *                                  onto the points by spgan_gather_csr + spgan_scatter_slots
+ *   spgan_pointconv_aggregate:     E[q, c*W + w] = sum_k F[q*K+k, c] * dens[q*K+k] * Wt[q*K+k, w]; F [Q*K,C], Wt [Q*K,W], dens [Q*K] or NULL,
+ *                                  W = 16 (the reference's only width); any K (walked in chunks), any C; sum in ascending k
+ *                                  (v_mfma_f32_16x16x4_f32: exact fp32 products)                                   pointconv_util.py:373-377
+ *   spgan_pointconv_aggregate_bwd: dF [Q*K,C], dWt [Q*K,W], ddens [Q*K] (NULL exactly when dens is) from dE [Q, C*W] in one launch */
+int spgan_kde_density(const float* xyz, int B, int N, float bandwidth, float* density, float* inv_density, spgan_stream_t s);
+int spgan_kde_density_bwd(const float* xyz, const float* g, const float* ginv, const float* inv_density, int B, int N, float bandwidth,
+                          float* dxyz, spgan_stream_t s);
+int spgan_group_density_scale(const float* inv_density, const int64_t* idx, int B, int N, int S, int K, float* scale, int32_t* bad,
+                              spgan_stream_t s);
+int spgan_group_density_scale_bwd(const float* g, const float* inv_density, const int64_t* idx, int B, int N, int S, int K, float* dslot,
+                                  spgan_stream_t s);
+int spgan_pointconv_aggregate(const float* F, const float* Wt, const float* dens, int Q, int K, int C, int W, float* E, spgan_stream_t s);
+int spgan_pointconv_aggregate_bwd(const float* dE, const float* F, const float* Wt, const float* dens, int Q, int K, int C, int W, float* dF,
+                                  float* dWt, float* ddens, spgan_stream_t s);
 /* Per-channel scalar algebra of the double backward, one launch each:
  *   coeffs out4C = [dgammaA | sbarA | xsum0 | xsum1];  phaseb: sums2C = [xsum0+gamma*s0 | xsum1+gamma*s1+invstd*sbarA], dgamma = dgammaA+s1 */
 int spgan_bn_dbl_coeffs(const float* U0, const float* U1, const float* Ugz, const float* S0, const float* S1, const float* gamma,

@@ -272,6 +272,12 @@ SIGNATURES = {
     "spgan_group_max_bwd": (I, [P, P, P, P, I, P, P, F, I, I, I, P, P, P]),
     "spgan_cm_to_rows": (I, [P, I, I, I, P, I, I, P]),
     "spgan_rows_to_cm": (I, [P, I, I, I, I, I, P, P]),
+    "spgan_kde_density": (I, [P, I, I, F, P, P, P]),
+    "spgan_kde_density_bwd": (I, [P, P, P, P, I, I, F, P, P]),
+    "spgan_group_density_scale": (I, [P, P, I, I, I, I, P, P, P]),
+    "spgan_group_density_scale_bwd": (I, [P, P, P, I, I, I, I, P, P]),
+    "spgan_pointconv_aggregate": (I, [P, P, P, I, I, I, I, P, P]),
+    "spgan_pointconv_aggregate_bwd": (I, [P, P, P, P, I, I, I, I, P, P, P, P]),
     "spgan_nn_distance": (I, [P, P, I, I, I, P, P, P]),
     "spgan_chamfer_bwd": (I, [P, P, I, I, I, P, P, P, P, P, P]),
     "spgan_chamfer_pairs": (I, [P, P, I, I, I, I, P, P]),

@@ -428,9 +428,22 @@ class _SharedMLPFn(torch.autograd.Function):
                 sums = torch.cat([s0, s1])
             else:
                 grads[0] = ops.gemm_tn(dy, a0).view_as(W)
+                if ctx.training and W2.shape[1] == 1:
+                    grads[0] = _one_column_wgrad(grads[0], W, gamma, sums[Cn:], inv)
                 if ctx.needs_input_grad[1]:
                     da0 = ops.gemm_nt(dy, W2.t().contiguous())
         return (None, da0) + tuple(g_ if need else None for g_, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+def _one_column_wgrad(plain: Tensor, W: Tensor, gamma: Tensor, s1: Tensor, invstd: Tensor) -> Tensor:
+    """Weight gradient of a layer with ONE input column in front of a train-mode BatchNorm (PointConv's DensityNet).  y = w*s + b is
+    normalised, so the output does not depend on |w| and sum_r dy_r*s_r cancels down to a residue of order eps: with
+    dy = gamma*invstd*(g - mean g - xhat*mean(g*xhat)) and s - mean s = (y - mean y)/w,
+        dW = (gamma/w) * S1 * (1 - var*invstd^2) = gamma * S1 * eps * invstd^2 / w,      S1 = sum_r g_r*xhat_r (the BatchNorm weight's gradient).
+    The product form has no cancellation; the row sum (`plain`) is kept where w == 0, where the identity does not apply."""
+    w = W.view(-1)
+    closed = gamma * s1 * (ops.BN_EPS * invstd * invstd) / torch.where(w != 0, w, torch.ones_like(w))
+    return torch.where(w != 0, closed, plain.view(-1)).view_as(W)
 
 
 def _mlp_params(convs, bns):
