@@ -676,6 +676,32 @@ int spgan_group_density_scale_bwd(const float* g, const float* inv_density, cons
 int spgan_pointconv_aggregate(const float* F, const float* Wt, const float* dens, int Q, int K, int C, int W, float* E, spgan_stream_t s);
 int spgan_pointconv_aggregate_bwd(const float* dE, const float* F, const float* Wt, const float* dens, int Q, int K, int C, int W, float* dF,
                                   float* dWt, float* ddens, spgan_stream_t s);
+/* Max-aggregation edge convolution (Generation/modules.py:779-796).  PQ [M, >= 2F] = [P | Q] with P = Wd x,
+ * Q = (Wc - Wd) x + b; the pre-norm value of edge (i, j) is Q[i] + P[idx[i,j]]; idx int32 [M,k] global rows, 1 <= k <= 127.  No [M*k, F]
+ * tensor is read or written.  Deterministic: fixed summation orders, no float atomics.
+ *   spgan_edge_max_gather:    train (scale == NULL): pmax / pmin [M,F] = max / min over j of P[idx[i,j]], rmax / rmin [M,F] their ranks j
+ *                             (first rank on an exact tie), partials [ceil(M / tile_points)][F][2] = (sum, centred M2)
+ *                             of the M*k edge values (finalize-mode-0 records with tile_rows = tile_points * k; shift / out / sel NULL).
+ *                             eval (scale, shift given; the four train outputs NULL, partials optional): out and sel of spgan_edge_max_finish
+ *                             in the same pass.
+ *   spgan_edge_max_finish:    out[i,c] = relu(scale*(Q + (scale >= 0 ? pmax : pmin)) + shift); sel = the rank of the chosen neighbour, bit 7 set
+ *                             where the ReLU clipped.
+ *   spgan_edge_max_bwd_point: g [M,F] is overwritten with r = g * 1[out > 0]; partials [ceil(M / tile_points)][F][2] = plain sums
+ *                             (sum r, sum r * xhat(i, sel, c)), xhat = (Q + P[sel] - mean) * invstd  (finalize mode 1, tile_rows = tile_points).
+ *   spgan_edge_max_bwd_graph: dPQ [M, ldd >= 2F] = [dP | dQ] over the in-edge lists of spgan_csr_build.  sums = [sum r | sum r*xhat] (2F): the
+ *                             train-mode BatchNorm terms (idx, mean, invstd required; sum_j P[idx[m,j]] is gathered again); sums == NULL: eval mode, dQ = scale*r and
+ *                             dP[m] = scale * sum of r over the in-edges whose rank was selected. */
+int spgan_edge_max_tile_points(void);
+int spgan_edge_max_gather(const float* PQ, int ld, const int32_t* idx, int M, int k, int F, float* pmax, float* pmin, uint8_t* rmax,
+                          uint8_t* rmin, float* partials, const float* scale, const float* shift, float* out, uint8_t* sel,
+                          spgan_stream_t s);
+int spgan_edge_max_finish(const float* PQ, int ld, const float* pmax, const float* pmin, const uint8_t* rmax, const uint8_t* rmin,
+                          const float* scale, const float* shift, int M, int F, float* out, uint8_t* sel, spgan_stream_t s);
+int spgan_edge_max_bwd_point(float* g, const uint8_t* sel, const float* PQ, int ld, const int32_t* idx, int M, int k, int F, const float* mean,
+                             const float* invstd, float* partials, spgan_stream_t s);
+int spgan_edge_max_bwd_graph(const float* r, const uint8_t* sel, const float* PQ, int ld, const int32_t* rowptr, const int32_t* src,
+                             const int32_t* idx, int M, int k, int F, const float* scale, const float* mean, const float* invstd,
+                             const float* sums, float* dPQ, int ldd, spgan_stream_t s);
 /* Per-channel scalar algebra of the double backward, one launch each:
  *   coeffs out4C = [dgammaA | sbarA | xsum0 | xsum1];  phaseb: sums2C = [xsum0+gamma*s0 | xsum1+gamma*s1+invstd*sbarA], dgamma = dgammaA+s1 */
 int spgan_bn_dbl_coeffs(const float* U0, const float* U1, const float* Ugz, const float* S0, const float* S1, const float* gamma,

@@ -278,6 +278,11 @@ SIGNATURES = {
     "spgan_group_density_scale_bwd": (I, [P, P, P, I, I, I, I, P, P]),
     "spgan_pointconv_aggregate": (I, [P, P, P, I, I, I, I, P, P]),
     "spgan_pointconv_aggregate_bwd": (I, [P, P, P, P, I, I, I, I, P, P, P, P]),
+    "spgan_edge_max_tile_points": (I, []),
+    "spgan_edge_max_gather": (I, [P, I, P, I, I, I, P, P, P, P, P, P, P, P, P, P]),
+    "spgan_edge_max_finish": (I, [P, I, P, P, P, P, P, P, I, I, P, P, P]),
+    "spgan_edge_max_bwd_point": (I, [P, P, P, I, P, I, I, I, P, P, P, P]),
+    "spgan_edge_max_bwd_graph": (I, [P, P, P, I, P, P, P, I, I, I, P, P, P, P, P, I, P]),
     "spgan_nn_distance": (I, [P, P, I, I, I, P, P, P]),
     "spgan_chamfer_bwd": (I, [P, P, I, I, I, P, P, P, P, P, P]),
     "spgan_chamfer_pairs": (I, [P, P, I, I, I, I, P, P]),

@@ -13,8 +13,9 @@ import threading
 
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
-from . import nets, ops
+from . import edge_max, nets, ops
 
 Tensor = torch.Tensor
 
@@ -536,6 +537,79 @@ class EdgeBlockFn(Function):
                 cache["csr"] = csr
         dx, g = nets.edgeblock_backward(P, h.prefix, ctx.ectx, dout, csr, need_dx=ctx.needs_input_grad[1])
         return (None, dx) + _deliver(params, [g[n] for n in h.names], ctx.needs_input_grad[2:], ctx.fused)
+
+
+class EdgeMaxConvFn(Function):
+    """out [B,F,N] = max_j relu(bn(conv1x1(cat[x_i, x_j - x_i])))   (the reference's edgeConv, Generation/modules.py:779-796) without the
+    [B,2Fin,N,k] edge tensor: one per-point GEMM PQ = x.[Wd ; Wc - Wd]^T + [0 ; b] and gather passes over it (csrc/edge_max.hip).
+    inputs: holder(B, N, k, training, idx | None, knn_mode, bn = the nn.BatchNorm2d module), x [B,Fin,N], conv weight [F,2Fin,1,1], conv bias,
+    bn weight, bn bias.  Once differentiable: the selection of the max is piecewise constant and the backward is a closed form over
+    saved statistics, so a second derivative through it is refused (no GradientPenalty on top of this layer)."""
+
+    @staticmethod
+    def forward(ctx, h, x, W, b, gamma, beta):
+        B, Fin, N = x.shape
+        F_ = W.shape[0]
+        bn = h.bn
+        x_pm = ops.cm_to_pm(x)
+        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, h.k, h.knn_mode)
+        W2 = W.reshape(F_, 2 * Fin)
+        Wd = W2[:, Fin:]
+        Wst = torch.cat([Wd, W2[:, :Fin] - Wd], dim=0)                   # [2F, Fin]: rows of P, then rows of Q
+        PQ = ops.gemm_nt(x_pm, Wst, torch.cat([torch.zeros_like(b), b]))
+        if h.training:
+            pmax, pmin, rmax, rmin, part, tile_rows = edge_max.edge_max_gather(PQ, idx)
+            st = edge_max.edge_max_bn(part, tile_rows, idx.numel(), gamma, beta, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
+            bn.num_batches_tracked += 1
+            out_pm, sel = edge_max.edge_max_finish(PQ, pmax, pmin, rmax, rmin, st[0], st[1])
+            del pmax, pmin, rmax, rmin
+        else:
+            st = ops.bn_prepare(None, None, gamma, beta, idx.numel(), False, bn.running_mean, bn.running_var, eps=float(bn.eps))
+            out_pm, sel = edge_max.edge_max_eval(PQ, idx, st[0], st[1])
+        h.last_idx, h.last_sel = idx, sel
+        # st (scale, shift, invstd, mean) is made here and handed to nobody else: nothing can write it between forward and backward, so it
+        # rides on ctx like the other Functions' statistics (ctx.bns of the shared MLP) instead of through save_for_backward's version
+        # check.  The running statistics that ARE updated in place above are not read by the backward.
+        ctx.h, ctx.Fin, ctx.st = h, Fin, (st[0], st[1], st[2], st[3])
+        ctx.save_for_backward(x, PQ, sel, idx, Wst)          # x, not its point-major copy: the input is alive anyway
+        return ops.pm_to_cm(out_pm, B, N)
+
+    @staticmethod
+    def backward(ctx, dout):
+        # @once_differentiable alone fails late and only when the cotangent carries a graph; with create_graph=True and a plain cotangent
+        # (autograd.grad(out.sum(), x, create_graph=True): the gradient-penalty pattern) it would hand back a gradient without a graph and
+        # the penalty's second derivative would silently be missing.  Refuse where the request is made.
+        if torch.is_grad_enabled():
+            raise RuntimeError("edgeConv is once differentiable: its backward was asked to build a graph (create_graph=True), but it has no "
+                               "double backward -- the layer cannot sit under a gradient penalty")
+        return EdgeMaxConvFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        x, PQ, sel, idx, Wst = ctx.saved_tensors
+        h, Fin = ctx.h, ctx.Fin
+        scale, _, invstd, mean = ctx.st
+        F_ = sel.shape[1]
+        r = ops.cm_to_pm(dout)                                           # a fresh [M,F] tensor: overwritten with g * 1[out > 0]
+        sums = edge_max.edge_max_bwd_point(r, sel, PQ, idx, mean, invstd)
+        rowptr, src = ops.csr_build(idx, h.B, h.N)
+        if h.training:
+            dPQ = edge_max.edge_max_bwd_graph(r, sel, PQ, h.k, rowptr, src, scale, idx, mean, invstd, sums)
+        else:
+            dPQ = edge_max.edge_max_bwd_graph(r, sel, PQ, h.k, rowptr, src, scale)
+        del r
+        need = ctx.needs_input_grad
+        dW = None
+        if need[2]:                                                      # first: its split-K workspace and the point rows die before dx is made
+            dWst = ops.gemm_tn(dPQ, ops.cm_to_pm(x))                     # [2F, Fin]: rows of dW'_P, then of dW'_Q
+            dW = torch.cat([dWst[F_:], dWst[:F_] - dWst[F_:]], dim=1).view(F_, 2 * Fin, 1, 1)       # dWc = dW'_Q, dWd = dW'_P - dW'_Q
+        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wst.t().contiguous()), h.B, h.N) if need[1] else None
+        db = None
+        if need[3]:
+            # a bias in front of a train-mode BatchNorm: sum dQ is exactly zero (the batch mean absorbs it)
+            db = torch.zeros(F_, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dPQ[:, F_:])[0]
+        return None, dx, dW, db, (sums[F_:].clone() if need[4] else None), (sums[:F_].clone() if need[5] else None)
 
 
 class EdgeFeaturesFn(Function):

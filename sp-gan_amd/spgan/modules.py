@@ -607,3 +607,68 @@ def get_edge_features(x, k, num=-1, idx=None, return_idx=False):
     else:
         ee = ops.edge_features_cm(x, idx, k)
     return (ee, idx) if return_idx else ee
+
+
+class conv2dbr(nn.Module):
+    """Generation/modules.py:612-626: Conv2d -> BatchNorm2d -> ReLU, [B,Fin,H,W] -> [B,Fout,H,W].  Only the 1x1 / stride-1 case runs (a GEMM
+    over the B*H*W positions with the BatchNorm statistics in its epilogue: the shared-MLP layer path of pointnet_util); the module is
+    the parameter container of `edgeConv`, whose forward never materialises this layer's input."""
+
+    def __init__(self, Fin, Fout, kernel_size, stride=[1, 1]):
+        super().__init__()
+        self.conv = nn.Conv2d(Fin, Fout, kernel_size, stride)
+        self.bn = nn.BatchNorm2d(Fout)
+        self.ac = nn.ReLU(True)
+
+    def forward(self, x):
+        _require_gpu(x, "conv2dbr")
+        if tuple(self.conv.kernel_size) != (1, 1) or tuple(self.conv.stride) != (1, 1):
+            raise NotImplementedError("conv2dbr runs only the 1x1, stride-1 convolution (kernel_size %s, stride %s)"
+                                      % (tuple(self.conv.kernel_size), tuple(self.conv.stride)))
+        from . import pointnet_util
+        B, C, H, W = x.shape
+        rows = x.permute(0, 2, 3, 1).reshape(B * H * W, C)
+        out = pointnet_util._shared_mlp(rows, 1, [self.conv], [self.bn], self.training)
+        return out.view(B, H, W, -1).permute(0, 3, 1, 2)
+
+
+class edgeConv(nn.Module):
+    """Generation/modules.py:779-796: max over the k neighbours of conv2dbr(get_edge_features(x)), [B,Fin,N] -> [B,Fout,N], evaluated per
+    point (Fn.EdgeMaxConvFn): no [B,2Fin,N,k] tensor in forward or backward.  idx (an extension): the graph to use instead of the kNN
+    graph of x, int64 [B, N*k] local indices as get_edge_features returns them (or int32 [B*N,k] global rows: the layer's own format, trusted -- only
+    int64 graphs are range-checked).  A negative bn.weight
+    entry takes the min branch.  Once differentiable.  last_idx / last_sel: the graph and the selected ranks of the latest forward."""
+
+    def __init__(self, Fin, Fout, k):
+        super().__init__()
+        if not 1 <= k <= 127:
+            raise ValueError("edgeConv: k must lie in 1..127")
+        self.k = k
+        self.Fin = Fin
+        self.Fout = Fout
+        self.conv = conv2dbr(2 * Fin, Fout, 1)
+        self.last_idx: Optional[torch.Tensor] = None
+        self.last_sel: Optional[torch.Tensor] = None
+
+    def forward(self, x, idx: Optional[torch.Tensor] = None):
+        _require_gpu(x, "edgeConv")
+        B, Fin, N = x.shape
+        if Fin != self.Fin:
+            raise ValueError("edgeConv(%d, %d, %d) got an input with %d channels" % (self.Fin, self.Fout, self.k, Fin))
+        bn = self.conv.bn
+        if bn.momentum is None or not bn.track_running_stats:
+            raise NotImplementedError("edgeConv: BatchNorm2d with momentum=None or track_running_stats=False is not supported")
+        if idx is not None:
+            _require_gpu(idx, "edgeConv idx")
+            if idx.dtype == torch.int64:
+                if idx.numel() != B * N * self.k:
+                    raise ValueError("edgeConv: idx must hold B*N*k = %d indices, got %s" % (B * N * self.k, tuple(idx.shape)))
+                if not ops.capturing() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+                    raise IndexError("edgeConv: a neighbour index lies outside [0, %d)" % N)
+                idx = ops.idx_from_local64(idx.reshape(B, N * self.k), B, N, self.k)
+            elif idx.dtype != torch.int32 or tuple(idx.shape) != (B * N, self.k):
+                raise ValueError("edgeConv: idx must be int64 [B, N*k] (local) or int32 [B*N, k] (global rows)")
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=1 if Fin <= 4 else 0, bn=bn, last_idx=None, last_sel=None)
+        out = Fn.EdgeMaxConvFn.apply(h, x.contiguous(), self.conv.conv.weight, self.conv.conv.bias, bn.weight, bn.bias)
+        self.last_idx, self.last_sel = h.last_idx, h.last_sel
+        return out
