@@ -82,18 +82,21 @@ def chunk_sums(mat: np.ndarray, batch_size: int) -> np.ndarray:
     return np.stack([mat[:, lo:lo + batch_size].sum(1) for lo in range(0, mat.shape[1], batch_size)], axis=1)
 
 
-def knn_pm(Mxx, Mxy, Myy, k: int, sqrt: bool = False) -> float:
-    """GAN_metrics.KNN: labels -1 / +1, k nearest other clouds by (distance, index), a vote >= 0 predicts +1."""
-    Mxx, Mxy, Myy = (np.asarray(x, np.float64) for x in (Mxx, Mxy, Myy))
+def knn_pm(Mxx, Mxy, Myy, k: int, sqrt: bool = False, return_pred: bool = False):
+    """GAN_metrics.KNN: labels -1 / +1, k nearest other clouds by (distance, index), a vote >= 0 predicts +1.  The matrices are
+    float32, and with `sqrt` so are the roots (as in the reference and the kernel: two float32 values may share a float32 root).
+    -> the accuracy; with return_pred also the +-1 predictions (int32 [n0 + n1])."""
+    Mxx, Mxy, Myy = (np.asarray(x, np.float32) for x in (Mxx, Mxy, Myy))
     n0, n1 = Mxx.shape[0], Myy.shape[0]
     M = np.block([[Mxx, Mxy], [Mxy.T, Myy]])
     if sqrt:
-        M = np.sqrt(np.abs(M))
-    M = M + np.diag(np.full(n0 + n1, np.inf))
+        M = np.sqrt(np.abs(M)).astype(np.float32)
+    M = M.astype(np.float64) + np.diag(np.full(n0 + n1, np.inf))
     label = np.concatenate([-np.ones(n0), np.ones(n1)])
     idx = np.argsort(M, axis=0, kind="stable")[:k]
     pred = np.where(label[idx].sum(0) >= 0, 1.0, -1.0)
-    return float((pred == label).mean())
+    acc = float((pred == label).mean())
+    return (acc, pred.astype(np.int32)) if return_pred else acc
 
 
 def voxel_counts(clouds, res: int = 28) -> np.ndarray:
