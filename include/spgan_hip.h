@@ -702,6 +702,31 @@ int spgan_edge_max_bwd_point(float* g, const uint8_t* sel, const float* PQ, int 
 int spgan_edge_max_bwd_graph(const float* r, const uint8_t* sel, const float* PQ, int ld, const int32_t* rowptr, const int32_t* src,
                              const int32_t* idx, int M, int k, int F, const float* scale, const float* mean, const float* invstd,
                              const float* sums, float* dPQ, int ldd, spgan_stream_t s);
+/* Rank-window edge convolution (csrc/edge_window.hip): the [1,w] Conv2d layers of upsample_edgeConv (Generation/modules.py:799-845) over
+ * get_edge_features(x), as fp32 MFMA products over gathered neighbour rows.  x [M, ldx >= C] point-major, idx int32 [M,k] global rows
+ * (a row outside [0,M) counts as the point itself: a zero difference), 1 <= w <= k <= 28, T = k - w + 1 window positions per point,
+ * d(i,j) = x[idx[i,j]] - x[i].  Deterministic: fixed summation orders, no float atomics.
+ *   spgan_edge_window_gemm:    Y[(i*T + t), o] = sum_{r<w, c<C} W[o, r*C + c] * d(i,t+r,c) + rowadd[i,o] + add2[(i*T + t), o]   (addends optional);
+ *                              W [O, ldw >= w*C] = the difference half of the conv weight, tap-major.  partials (optional)
+ *                              [ceil(M / tile_points(k,T))][O][2] = (sum, centred M2) of Y's columns: finalize-mode-0 records with
+ *                              tile_rows = tile_points * T (spgan_colstats_finalize_bn).
+ *   spgan_edge_window_wgrad:   dW[o, r*C + c] = sum_{i,t} G[(i*T + t), o] * d(i,t+r,c)   (dW [O, lddw >= w*C]); ws >= spgan_edge_window_wgrad_ws_bytes:
+ *                              partial sums per point range, reduced in ascending range order.
+ *   spgan_edge_window_dgrad:   S[i,j,c] (+)= sum_{t+r=j} sum_o G[(i*T + t), o] * Wt[r*C + c, o]   (Wt [w*C, ldwt >= O] = W transposed; S [M,k,C]
+ *                              contiguous; accumulate != 0 adds to S).
+ *   spgan_edge_window_scatter: dx[m,c] = add_a[m,c] + add_b[m,c] - sum_j S[m,j,c] + sum_{e in in(m)} S[e,c] over the in-edge lists of
+ *                              spgan_csr_build (ascending edge ids); addends optional. */
+int spgan_edge_window_tile_points(int k, int T);
+int spgan_edge_window_gemm(const float* x, int ldx, const int32_t* idx, int M, int k, int C, const float* W, int ldw, int O, int w,
+                           const float* rowadd, int ld_rowadd, const float* add2, int ld_add2, float* Y, int ldy, float* partials,
+                           spgan_stream_t s);
+size_t spgan_edge_window_wgrad_ws_bytes(int M, int k, int C, int O, int w);
+int spgan_edge_window_wgrad(const float* x, int ldx, const int32_t* idx, int M, int k, int C, const float* G, int ldg, int O, int w, float* dW,
+                            int lddw, float* ws, size_t ws_bytes, spgan_stream_t s);
+int spgan_edge_window_dgrad(const float* G, int ldg, const float* Wt, int ldwt, int M, int k, int C, int O, int w, float* S, int accumulate,
+                            spgan_stream_t s);
+int spgan_edge_window_scatter(const float* S, const int32_t* rowptr, const int32_t* src, int M, int k, int C, const float* add_a, int ld_a,
+                              const float* add_b, int ld_b, float* dx, int lddx, spgan_stream_t s);
 /* Per-channel scalar algebra of the double backward, one launch each:
  *   coeffs out4C = [dgammaA | sbarA | xsum0 | xsum1];  phaseb: sums2C = [xsum0+gamma*s0 | xsum1+gamma*s1+invstd*sbarA], dgamma = dgammaA+s1 */
 int spgan_bn_dbl_coeffs(const float* U0, const float* U1, const float* Ugz, const float* S0, const float* S1, const float* gamma,

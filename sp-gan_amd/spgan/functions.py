@@ -15,7 +15,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import edge_max, nets, ops
+from . import edge_max, edge_window, nets, ops
 
 Tensor = torch.Tensor
 
@@ -610,6 +610,154 @@ class EdgeMaxConvFn(Function):
             # a bias in front of a train-mode BatchNorm: sum dQ is exactly zero (the batch mean absorbs it)
             db = torch.zeros(F_, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dPQ[:, F_:])[0]
         return None, dx, dW, db, (sums[F_:].clone() if need[4] else None), (sums[:F_].clone() if need[5] else None)
+
+
+_UPSAMPLE_IMAGES: Dict[tuple, tuple] = {}
+
+
+def upsample_images(W1: Tensor, V: Tensor, C: int, k: int):
+    """The operand images of upsample_edgeConv's two conv weights (W1 [4C,2C,1,w], V [F2,2C,1,2k]):
+    (Wc1 [4C,C], Wd1 [4C,w*C], Wd1^T, Vc [F2,C], Vd [F2,k*C], Vd^T, V2p [F2,T*4C], V2p^T, Wc1^T, Vc^T).
+    Wc = the central halves summed over the taps; Wd = the difference halves, tap-major; V2p = conv2's last k taps with the columns
+    permuted from the reference's per-point (2C, k) reading, c'*k + j = o*T + t, to this layer's row order t*4C + o.
+    Cached per weight pair until a weight changes (torch's version counter, or an optimiser step of spgan.optim.Adam: the staleness rule
+    of nets._t).  Inside a capture the cache is neither read nor written: the images are rebuilt there, so that their kernels are part
+    of the graph and every replay sees the weights of that moment."""
+    def build():
+        w = W1.shape[3]
+        T = k - w + 1
+        F2 = V.shape[0]
+        Wc1 = W1[:, :C, 0, :].sum(dim=2)
+        Wd1 = W1[:, C:, 0, :].permute(0, 2, 1).reshape(4 * C, w * C)
+        Vc = V[:, :C, 0, :k].sum(dim=2)
+        Vd = V[:, C:, 0, :k].permute(0, 2, 1).reshape(F2, k * C)
+        V2p = V[:, :, 0, k:].reshape(F2, 4 * C, T).permute(0, 2, 1).reshape(F2, T * 4 * C)
+        return (Wc1, Wd1, Wd1.t().contiguous(), Vc, Vd, Vd.t().contiguous(), V2p, V2p.t().contiguous(), Wc1.t().contiguous(),
+                Vc.t().contiguous())
+    W1, V = W1.detach(), V.detach()
+    if ops.capturing():
+        return build()
+    key = (W1.data_ptr(), V.data_ptr(), tuple(W1.shape), tuple(V.shape), C, k)
+    stamp = (ops.weights_epoch_of(W1), ops.weights_epoch_of(V), W1._version, V._version)
+    hit = _UPSAMPLE_IMAGES.get(key)
+    if hit is not None and hit[0] == stamp:
+        return hit[1]
+    if len(_UPSAMPLE_IMAGES) >= 64:
+        _UPSAMPLE_IMAGES.clear()
+    img = build()
+    _UPSAMPLE_IMAGES[key] = (stamp, img)
+    return img
+
+
+class UpsampleEdgeConvFn(Function):
+    """out [B,Fout,2N] = the reference's upsample_edgeConv (Generation/modules.py:799-845) without the [B,2Fin,N,k] edge tensor, the
+    [B,4Fin,N,k/2] chain behind inte_conv_hk or the merged [B,2Fin,N,2k] tensor: both [1,w] convolutions are products over gathered
+    neighbour rows (csrc/edge_window.hip), their central halves per-point GEMMs, the transpose / view chain a column permutation of
+    conv2's weight (upsample_images), the final view free in a channel-major result.
+    inputs: holder(B, N, k, training, idx | None, knn_mode, slope, bn1, bn2 = the nn.BatchNorm2d modules), x [B,Fin,N], then
+    inte_conv_hk's conv weight, conv bias, bn weight, bn bias and conv2's.  Saved: x, the graph, the pre-norm U [M*T,4Fin] (the one
+    edge-sized tensor), the pre-norm y [M,2Fout] and the statistics.  Once differentiable, as EdgeMaxConvFn."""
+
+    @staticmethod
+    def forward(ctx, h, x, W1, b1, g1, be1, V, b2, g2, be2):
+        B, C, N = x.shape
+        k, M = h.k, B * N
+        T = k - W1.shape[3] + 1
+        bn1, bn2 = h.bn1, h.bn2
+        x_pm = ops.cm_to_pm(x)
+        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
+        Wc1, Wd1, _, Vc, Vd, _, V2p, _, _, _ = upsample_images(W1, V, C, k)
+        Q1 = ops.gemm_nt(x_pm, Wc1, b1)
+        if h.training:
+            U, part, rows = edge_window.edge_window_gemm(x_pm, idx, Wd1, rowadd=Q1, stats=True)
+            st1 = edge_max.edge_max_bn(part, rows, M * T, g1, be1, bn1.running_mean, bn1.running_var, float(bn1.momentum), float(bn1.eps))
+            bn1.num_batches_tracked += 1
+        else:
+            U = edge_window.edge_window_gemm(x_pm, idx, Wd1, rowadd=Q1)
+            st1 = ops.bn_prepare(None, None, g1, be1, M * T, False, bn1.running_mean, bn1.running_var, eps=float(bn1.eps))
+        del Q1
+        # the activated inte tensor is never stored: BatchNorm + LeakyReLU run in the prologue of the product that consumes it
+        st1r = (st1 if isinstance(st1, Tensor) else torch.stack(list(st1))).repeat(1, T)         # per column t*4C + o of the [M, T*4C] view
+        Y3 = ops.gemm_nt(U.view(M, T * 4 * C), V2p, pro=(st1r[0], st1r[1], h.slope))
+        Q2 = ops.gemm_nt(x_pm, Vc, b2)
+        if h.training:
+            Y, part, rows = edge_window.edge_window_gemm(x_pm, idx, Vd, rowadd=Q2, add2=Y3, stats=True)
+            st2 = edge_max.edge_max_bn(part, rows, M, g2, be2, bn2.running_mean, bn2.running_var, float(bn2.momentum), float(bn2.eps))
+            bn2.num_batches_tracked += 1
+        else:
+            Y = edge_window.edge_window_gemm(x_pm, idx, Vd, rowadd=Q2, add2=Y3)
+            st2 = ops.bn_prepare(None, None, g2, be2, M, False, bn2.running_mean, bn2.running_var, eps=float(bn2.eps))
+        del Q2, Y3
+        out_pm = ops.affine_act(Y, st2[0], st2[1], 0.0)
+        h.last_idx = idx
+        # the statistics are made here and handed to nobody else: they ride on ctx (see EdgeMaxConvFn)
+        ctx.h, ctx.st1, ctx.st2, ctx.st1r = h, tuple(st1[i] for i in range(4)), tuple(st2[i] for i in range(4)), st1r
+        ctx.save_for_backward(x, U, Y, idx, W1, V, g1, g2)
+        return ops.pm_to_cm(out_pm, B, N).view(B, V.shape[0] // 2, 2 * N)          # out[b, f, s*N + n] = y[b, 2f+s, n]: a view
+
+    @staticmethod
+    def backward(ctx, dout):
+        if torch.is_grad_enabled():
+            raise RuntimeError("upsample_edgeConv is once differentiable: its backward was asked to build a graph (create_graph=True), but "
+                               "it has no double backward -- the layer cannot sit under a gradient penalty")
+        return UpsampleEdgeConvFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        from . import pointnet_util
+        x, U, Y, idx, W1, V, g1, g2 = ctx.saved_tensors
+        h = ctx.h
+        B, C, N = x.shape
+        k, M = h.k, B * N
+        w = W1.shape[3]
+        T = k - w + 1
+        F2 = V.shape[0]
+        sc1, sh1, inv1, mu1 = ctx.st1
+        sc2, sh2, inv2, mu2 = ctx.st2
+        need = ctx.needs_input_grad
+        Wc1, Wd1, Wd1t, Vc, Vd, Vdt, V2p, V2pt, Wc1t, Vct = upsample_images(W1, V, C, k)
+        x_pm = ops.cm_to_pm(x)
+        # ReLU + BatchNorm of conv2
+        g = ops.cm_to_pm(dout.reshape(B, F2, N).contiguous())
+        r, sums2 = pointnet_util._group_max_bwd(g, ops.affine_act(Y, sc2, sh2, 0.0), None, Y, mu2, inv2, 0.0, 1)
+        dy = ops.bn_bwd_apply(r, Y, mu2, inv2, g2, sums2 if h.training else torch.zeros_like(sums2), M)
+        del g, r
+        Uf = U.view(M, T * 4 * C)
+        sc1r, sh1r, inv1r, mu1r = ctx.st1r[0], ctx.st1r[1], ctx.st1r[2], ctx.st1r[3]
+        dV = None
+        if need[6]:
+            dV = torch.empty_like(V)
+            dV[:, :C, 0, :k] = ops.gemm_tn(dy, x_pm).unsqueeze(2)
+            dV[:, C:, 0, :k] = edge_window.edge_window_wgrad(x_pm, idx, dy, k).view(F2, k, C).permute(0, 2, 1)
+            dV[:, :, 0, k:] = ops.gemm_tn(dy, Uf, pro=(sc1r, sh1r, h.slope)).view(F2, T, 4 * C).permute(0, 2, 1).reshape(F2, 2 * C, k)
+        # LeakyReLU + BatchNorm of inte_conv_hk: the mask and the column sums come out of the product's epilogue
+        gz, t1, t2 = ops.gemm_nt_bnbwd(dy, V2pt, Uf, sc1r, sh1r, mu1r, inv1r, h.slope)
+        sums1 = torch.cat([t1.view(T, 4 * C).sum(dim=0), t2.view(T, 4 * C).sum(dim=0)])
+        dU = ops.bn_bwd_apply(gz.view(M * T, 4 * C), U, mu1, inv1, g1, sums1 if h.training else torch.zeros_like(sums1), M * T)
+        del gz
+        dQ1 = ops.colsum(dU, T)                                            # [M,4C]: the central half sees the sum over the window positions
+        dW1 = None
+        if need[2]:
+            dW1 = torch.empty_like(W1)
+            dW1[:, :C, 0, :] = ops.gemm_tn(dQ1, x_pm).unsqueeze(2)
+            dW1[:, C:, 0, :] = edge_window.edge_window_wgrad(x_pm, idx, dU, w).view(4 * C, w, C).permute(0, 2, 1)
+        dx = None
+        if need[1]:
+            S = edge_window.edge_window_dgrad(dU, Wd1t, k, C)              # [M,k,C]: the only per-edge tensor made here
+            edge_window.edge_window_dgrad(dy, Vdt, k, C, out=S)
+            rowptr, src = ops.csr_build(idx, B, N)
+            dx_pm = edge_window.edge_window_scatter(S, rowptr, src, ops.gemm_nt(dy, Vct), ops.gemm_nt(dQ1, Wc1t))
+            del S
+            dx = ops.pm_to_cm(dx_pm, B, N)
+        # a bias in front of a train-mode BatchNorm: exactly zero (the batch mean absorbs it)
+        db1 = db2 = None
+        if need[3]:
+            db1 = torch.zeros(4 * C, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dU)[0]
+        if need[7]:
+            db2 = torch.zeros(F2, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dy)[0]
+        return (None, dx, dW1, db1, sums1[4 * C:].clone() if need[4] else None, sums1[:4 * C].clone() if need[5] else None,
+                dV, db2, sums2[F2:].clone() if need[8] else None, sums2[:F2].clone() if need[9] else None)
 
 
 class EdgeFeaturesFn(Function):

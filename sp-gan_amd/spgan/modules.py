@@ -672,3 +672,70 @@ class edgeConv(nn.Module):
         out = Fn.EdgeMaxConvFn.apply(h, x.contiguous(), self.conv.conv.weight, self.conv.conv.bias, bn.weight, bn.bias)
         self.last_idx, self.last_sel = h.last_idx, h.last_sel
         return out
+
+
+def get_edge_features_xyz(x, pc, k, num=-1):
+    """Generation/modules.py:727-776: x [B,C,N], pc [B,3,N] -> (e_fea [B,2C,N,k], e_xyz [B,6,N,k]): ONE kNN graph, built in the feature
+    space of x, gathers both tensors (cat[central, neighbour-central] each).  Differentiable in x and pc through get_edge_features'
+    backward; the indices carry no gradient."""
+    _require_gpu(x, "get_edge_features_xyz")
+    _require_gpu(pc, "get_edge_features_xyz pc")
+    if pc.dim() != 3 or pc.shape[0] != x.shape[0] or pc.shape[1] != 3 or pc.shape[2] != x.shape[2]:
+        raise ValueError("get_edge_features_xyz: pc must be [B,3,N] for x [B,C,N], got %s and %s" % (tuple(pc.shape), tuple(x.shape)))
+    e_fea, idx = get_edge_features(x, k, num, return_idx=True)
+    return e_fea, get_edge_features(pc, k, num, idx=idx)
+
+
+class upsample_edgeConv(nn.Module):
+    """Generation/modules.py:799-845: the point-doubling edge convolution, [B,Fin,N] -> [B,Fout,2N]:
+    conv2(cat(ee, reshuffled inte_conv_hk(ee))) with ee = get_edge_features(x), evaluated over gathered neighbour rows
+    (Fn.UpsampleEdgeConvFn, csrc/edge_window.hip): neither ee nor the merged [B,2Fin,N,2k] tensor exists in forward or backward.
+    The sub-modules are parameter containers in the reference's order (state_dicts load strictly both ways); conv2 on its own still
+    refuses its [1,2k] kernel.  idx (an extension, as edgeConv's): the graph to use instead of the kNN graph of x, int64 [B, N*k] local
+    indices (range-checked outside a capture) or int32 [B*N,k] global rows (trusted).  Once differentiable.  last_idx: the graph of
+    the latest forward."""
+
+    def __init__(self, Fin, Fout, k, num):
+        super().__init__()
+        if k % 2 or k < 2:
+            raise ValueError("upsample_edgeConv: k must be even (the reference's view of the [.., k/2] tensor as [.., k] fails otherwise), got %d" % k)
+        if k > 28:
+            raise ValueError("upsample_edgeConv: k must not exceed 28")
+        self.k = k
+        self.Fin = Fin
+        self.Fout = Fout
+        self.num = num
+        self.conv2 = conv2dbr(2 * Fin, 2 * Fout, [1, 2 * k], [1, 1])
+        self.inte_conv_hk = nn.Sequential(
+            nn.Conv2d(2 * Fin, 4 * Fin, [1, k // 2 + 1], [1, 1]),
+            nn.BatchNorm2d(4 * Fin),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.last_idx: Optional[torch.Tensor] = None
+
+    def forward(self, x, idx: Optional[torch.Tensor] = None):
+        _require_gpu(x, "upsample_edgeConv")
+        B, Fin, N = x.shape
+        if Fin != self.Fin:
+            raise ValueError("upsample_edgeConv(%d, %d, %d) got an input with %d channels" % (self.Fin, self.Fout, self.k, Fin))
+        conv1, bn1, act = self.inte_conv_hk[0], self.inte_conv_hk[1], self.inte_conv_hk[2]
+        bn2 = self.conv2.bn
+        for bn in (bn1, bn2):
+            if bn.momentum is None or not bn.track_running_stats:
+                raise NotImplementedError("upsample_edgeConv: BatchNorm2d with momentum=None or track_running_stats=False is not supported")
+        if idx is not None:
+            _require_gpu(idx, "upsample_edgeConv idx")
+            if idx.dtype == torch.int64:
+                if idx.numel() != B * N * self.k:
+                    raise ValueError("upsample_edgeConv: idx must hold B*N*k = %d indices, got %s" % (B * N * self.k, tuple(idx.shape)))
+                if not ops.capturing() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+                    raise IndexError("upsample_edgeConv: a neighbour index lies outside [0, %d)" % N)
+                idx = ops.idx_from_local64(idx.reshape(B, N * self.k), B, N, self.k)
+            elif idx.dtype != torch.int32 or tuple(idx.shape) != (B * N, self.k):
+                raise ValueError("upsample_edgeConv: idx must be int64 [B, N*k] (local) or int32 [B*N, k] (global rows)")
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=1 if Fin <= 4 else 0, slope=float(act.negative_slope),
+                    bn1=bn1, bn2=bn2, last_idx=None)
+        out = Fn.UpsampleEdgeConvFn.apply(h, x.contiguous(), conv1.weight, conv1.bias, bn1.weight, bn1.bias,
+                                          self.conv2.conv.weight, self.conv2.conv.bias, bn2.weight, bn2.bias)
+        self.last_idx = h.last_idx
+        return out
