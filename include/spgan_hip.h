@@ -727,6 +727,33 @@ int spgan_edge_window_dgrad(const float* G, int ldg, const float* Wt, int ldwt, 
                             spgan_stream_t s);
 int spgan_edge_window_scatter(const float* S, const int32_t* rowptr, const int32_t* src, int M, int k, int C, const float* add_a, int ld_a,
                               const float* add_b, int ld_b, float* dx, int lddx, spgan_stream_t s);
+/* Full-rank edge convolution (csrc/edge_rank.hip): the core of deform_edgeConv_simple / deform_edgeConv_first (Generation/modules.py:1394-1466),
+ * Conv2d(2Fin -> F1, 1x1) + BatchNorm2d + LeakyReLU over the edge features, then Conv2d(F1 -> O, [1,k]) over the neighbour ranks.
+ * PQ [M, ld >= 2F1] = [P | Q] is the per-point GEMM's result (as for the max-aggregation layer), idx [M,k] global rows, and
+ * h(i,r,c) = lrelu(scale1[c] * (Q[i,c] + P[idx[i,r],c]) + shift1[c], slope) is formed inside the kernels, never stored.  1 <= k <= 32, any M, F1, O.
+ *   spgan_edge_rank_gemm:    Y[i,o] = b2[o] + sum_{r<k, c<F1} W2i[o, r*F1 + c] * h(i,r,c)   (W2i [O, ldw >= k*F1] tap-major; b2 optional);
+ *                            partials != NULL: [ceil(M / tile_points)][O][2] (sum, centred M2) records of Y's columns for
+ *                            spgan_colstats_finalize_bn (tile_rows = spgan_edge_rank_tile_points(k); 0: k unsupported).
+ *   spgan_edge_rank_wgrad:   dW2i[o, r*F1 + c] = sum_i dY[i,o] * h(i,r,c)   (dW2i [O, lddw >= k*F1]); ws >= spgan_edge_rank_wgrad_ws_bytes:
+ *                            the point ranges' partial products, summed in range order.
+ *   spgan_edge_rank_dgrad:   dA[i,r,c] = lrelu'(a(i,r,c)) * sum_o dY[i,o] * W2t[r*F1 + c, o]   (W2t [k*F1, ldwt >= O] = W2i transposed; dA [M,k,F1]
+ *                            contiguous; a = the BatchNorm output, its sign recomputed) and partials [ceil(M / tile_points)][F1][2] = plain sums
+ *                            (sum dA, sum dA * zhat), zhat = (Q + P - mean1) * invstd1, over the tile's points and all ranks (finalize mode 1).
+ *   spgan_edge_rank_scatter: dPQ [M, ldd >= 2F1] = [dP | dQ]: dz = scale1 * (dA - sums[c] / E - zhat * sums[F1 + c] / E), E = M*k (train: PQ, idx,
+ *                            mean1, invstd1 required) or scale1 * dA (sums == NULL: eval); dQ[i] = sum_r dz(i,r), dP[j] = sum of dz over the
+ *                            in-edge list of j (spgan_csr_build, ascending edge ids; in-degree 0: zeros). */
+int spgan_edge_rank_tile_points(int k);
+int spgan_edge_rank_gemm(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1, float slope,
+                         const float* W2i, int ldw, const float* b2, int O, float* Y, int ldy, float* partials, spgan_stream_t s);
+size_t spgan_edge_rank_wgrad_ws_bytes(int M, int k, int F1, int O);
+int spgan_edge_rank_wgrad(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1, float slope,
+                          const float* dY, int ldg, int O, float* dW2i, int lddw, float* ws, size_t ws_bytes, spgan_stream_t s);
+int spgan_edge_rank_dgrad(const float* dY, int ldg, const float* W2t, int ldwt, const float* PQ, int ld, const int32_t* idx, int M, int k, int F1,
+                          int O, const float* scale1, const float* shift1, const float* mean1, const float* invstd1, float slope, float* dA,
+                          float* partials, spgan_stream_t s);
+int spgan_edge_rank_scatter(const float* dA, const int32_t* rowptr, const int32_t* src, const float* PQ, int ld, const int32_t* idx, int M, int k,
+                            int F1, const float* scale1, const float* mean1, const float* invstd1, const float* sums, float* dPQ, int ldd,
+                            spgan_stream_t s);
 /* Per-channel scalar algebra of the double backward, one launch each:
  *   coeffs out4C = [dgammaA | sbarA | xsum0 | xsum1];  phaseb: sums2C = [xsum0+gamma*s0 | xsum1+gamma*s1+invstd*sbarA], dgamma = dgammaA+s1 */
 int spgan_bn_dbl_coeffs(const float* U0, const float* U1, const float* Ugz, const float* S0, const float* S1, const float* gamma,

@@ -1,0 +1,517 @@
+// Full-rank edge convolution: the core of the reference's deform_edgeConv_simple / deform_edgeConv_first (Generation/modules.py:1394-1466):
+// Conv2d(2Fin -> F1, 1x1) over get_edge_features, BatchNorm2d, LeakyReLU, then Conv2d(F1 -> O, [1,k]) that collapses the k neighbour
+// ranks with one weight per rank.
+//
+// With W1 = [Wc | Wd] the pre-norm value of edge (i, r) is z(i,r,:) = Q_i + P_n(i,r), P = x Wd^T, Q = x (Wc - Wd)^T + b1 (one per-point
+// GEMM -> PQ [M, 2F1] = [P | Q], as edge_max.hip), so the activated edge tensor h(i,r,c) = lrelu(scale1[c] * z + shift1[c]) is a
+// function of gathered rows of P and never has to exist in memory in forward:
+//   spgan_edge_rank_gemm     y[i,o] = b2[o] + sum_{r<k, c<F1} W2i[o, r*F1 + c] h(i,r,c): a product with K = k*F1 whose A operand is
+//                            formed in LDS.  A workgroup owns ER_PT points; per step it stages h of ER_RS ranks x ER_CK channels
+//                            (16 lanes fetch 256 contiguous bytes of one row of P: the whole row for F1 <= 64) and feeds
+//                            v_mfma_f32_16x16x4_f32 from there; the B operand comes straight from the weight image (L2).  Epilogue:
+//                            bias and the (sum, centred M2) column records of y (spgan_colstats_finalize_bn).
+//   spgan_edge_rank_wgrad    dW2i[o, r*F1 + c] = sum_i dy[i,o] h(i,r,c), h recomputed and staged the same way; a workgroup owns 128 output
+//                            channels x 64 input channels x ER_RB ranks of one point range; the ranges are summed in split order.
+//   spgan_edge_rank_dgrad    da(i,r,c) = lrelu'(a(i,r,c)) * sum_o dy[i,o] W2i[o, r*F1 + c]  [M,k,F1] (the one per-edge buffer, backward
+//                            only), a plain MFMA product per rank with both operands from global memory / L2 (W2t = the transposed
+//                            image [k*F1, O]); the epilogue recomputes the sign of a = scale1 * z + shift1 and writes per-tile column
+//                            sums of da and da * zhat (zhat = (z - mean1) * invstd1), summed over points and ranks in a fixed order.
+//   spgan_edge_rank_scatter  dPQ [M, 2F1] = [dP | dQ] from da: dz = scale1 * (da - A - zhat * Bc) (train; A, Bc = the reduced sums / E) or
+//                            scale1 * da (eval); dQ_i = sum_r dz(i,r), dP_j = sum over the in-edge list of j (spgan_csr_build) in
+//                            ascending edge order.  No float atomics anywhere.
+//
+// MFMA operand order as in edge_window.hip: a 16-wide K block is one 16-byte fragment per lane (lane group g = lane>>4 holds K elements
+// 4g..4g+3), consumed by four MFMA steps; A and B agree on that order.  fp32 operands, fp32 accumulation: exact products.
+#include "common.hpp"
+
+namespace {
+
+constexpr int ER_KMAX = 32;
+constexpr int ER_PT = 32;               // points per workgroup of gemm / dgrad = rows of a statistics record
+constexpr int ER_CK = 64;               // channels staged per step
+constexpr int ER_RS = 4;                // ranks staged per step
+constexpr int ER_PST = ER_CK + 4;       // 4 (mod 32) floats between points: the 16 points of a ds_read_b128 group spread over all banks
+constexpr int ER_RB = 2;                // ranks per weight-gradient workgroup
+constexpr int ER_WPST = ER_CK + 8;      // ER_RB * ER_WPST = 16 (mod 32): the two point groups of a ds_read_b32 half hit disjoint banks
+
+__device__ __forceinline__ int xcd_block() {
+  const int per = gridDim.x >> 3;
+  return (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
+}
+inline int grid8(long n) { return (int)((n + 7) / 8 * 8); }
+
+// four consecutive floats of which the first `nvalid` exist (VEC: extents and addresses are multiples of 4 floats: all or nothing)
+template <bool VEC>
+__device__ __forceinline__ f32x4 ld4(const float* __restrict__ p, int nvalid) {
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (VEC) {
+    if (nvalid >= 4) v = *reinterpret_cast<const f32x4*>(p);
+  } else {
+    if (nvalid > 0) v.x = p[0];
+    if (nvalid > 1) v.y = p[1];
+    if (nvalid > 2) v.z = p[2];
+    if (nvalid > 3) v.w = p[3];
+  }
+  return v;
+}
+
+__device__ __forceinline__ f32x4 mfma4(const f32x4& a, const f32x4& b, f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+  return acc;
+}
+
+__device__ __forceinline__ int neighbour(const int32_t* __restrict__ idx, int i, int k, int r, int M) {
+  const int n = idx[(size_t)i * k + r];
+  return (unsigned)n >= (unsigned)M ? i : n;
+}
+
+// a = scale * (Q_i + P_n) + shift: every kernel forms it with these operations, so that the sign the backward recomputes is the forward's
+__device__ __forceinline__ float pre_act(float q, float p, float sc, float sh) { return fmaf(sc, q + p, sh); }
+
+// h(i, r, c..c+3) for r = the rank whose neighbour is n; channels past F1 give 0
+template <bool VEC>
+__device__ __forceinline__ f32x4 rank_h4(const float* __restrict__ PQ, int ld, int F1, int i, int n, int c, const float* __restrict__ sc,
+                                         const float* __restrict__ sh, float slope) {
+  const int nv = F1 - c;
+  const f32x4 p = ld4<VEC>(PQ + (size_t)n * ld + c, nv), q = ld4<VEC>(PQ + (size_t)i * ld + F1 + c, nv);
+  const f32x4 a = ld4<VEC>(sc + c, nv), s = ld4<VEC>(sh + c, nv);
+  f32x4 h;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) h[u] = lrelu_f(pre_act(q[u], p[u], a[u], s[u]), slope);
+  return h;
+}
+
+// ------------------------------------------------------------------------------------------ forward
+// Per wave: 2 blocks of 16 points x (2 groups of 128 columns) x 2 blocks of 16 output columns; the four waves of a workgroup take 128
+// consecutive output columns of each group, so one staging serves 256 output columns.
+template <bool VEC>
+__global__ __launch_bounds__(256, 2) void edge_rank_gemm_kernel(const float* __restrict__ PQ, int ld, const int32_t* __restrict__ idx, int M, int k,
+                                                                int F1, const float* __restrict__ sc, const float* __restrict__ sh, float slope,
+                                                                const float* __restrict__ W, int ldw, const float* __restrict__ b2, int O,
+                                                                float* __restrict__ Y, int ldy, float* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) float sm[ER_RS * ER_PT * ER_PST];
+  const int bx = xcd_block();
+  const int p0 = bx * ER_PT;
+  if (p0 >= M) return;
+  const int np = min(ER_PT, M - p0);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, g = lane >> 4;
+  const float cnt = (float)np;
+  for (int ob = 0; ob < O; ob += 256) {
+    const int oc0 = ob + wave * 32;                  // + og * 128 + cb * 16 + col
+    const bool wave_on = oc0 < O;                    // uniform per wave; idle waves still stage and meet the barriers
+    f32x4 acc[2][2][2];
+#pragma unroll
+    for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+      for (int og = 0; og < 2; ++og) acc[pb][og][0] = acc[pb][og][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int r0 = 0; r0 < k; r0 += ER_RS) {
+      const int nr = min(ER_RS, k - r0);
+      for (int c0 = 0; c0 < F1; c0 += ER_CK) {
+        __syncthreads();
+        for (int e = threadIdx.x; e < nr * ER_PT * (ER_CK / 4); e += 256) {
+          const int cc = (e & 15) * 4, p = (e >> 4) & (ER_PT - 1), rs = e >> 9;
+          f32x4 v = {0.f, 0.f, 0.f, 0.f};
+          if (p < np && c0 + cc < F1) {
+            const int i = p0 + p;
+            v = rank_h4<VEC>(PQ, ld, F1, i, neighbour(idx, i, k, r0 + rs, M), c0 + cc, sc, sh, slope);
+          }
+          *reinterpret_cast<f32x4*>(sm + (rs * ER_PT + p) * ER_PST + cc) = v;
+        }
+        __syncthreads();
+        if (!wave_on) continue;
+        const int nkb = (min(ER_CK, F1 - c0) + 15) >> 4;
+        for (int rs = 0; rs < nr; ++rs) {
+          for (int kb = 0; kb < nkb; ++kb) {
+            const int cc = kb * 16 + 4 * g;
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(sm + (rs * ER_PT + col) * ER_PST + cc);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(sm + (rs * ER_PT + 16 + col) * ER_PST + cc);
+#pragma unroll
+            for (int og = 0; og < 2; ++og) {
+              if (oc0 + og * 128 < O) {              // uniform per wave
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) {
+                  const int o = oc0 + og * 128 + cb * 16 + col;
+                  const f32x4 b = ld4<VEC>(W + (size_t)min(o, O - 1) * ldw + (size_t)(r0 + rs) * F1 + c0 + cc, o < O ? F1 - (c0 + cc) : 0);
+                  acc[0][og][cb] = mfma4(a0, b, acc[0][og][cb]);
+                  acc[1][og][cb] = mfma4(a1, b, acc[1][og][cb]);
+                }
+              }
+            }
+          }
+        }
+      }
+    }
+    if (!wave_on) continue;
+    // epilogue: the D fragment of a lane is rows (points) 4g..4g+3 of column col
+#pragma unroll
+    for (int og = 0; og < 2; ++og) {
+      if (oc0 + og * 128 >= O) continue;             // uniform per wave
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) {
+        const int o = oc0 + og * 128 + cb * 16 + col;
+        const float bias = (b2 && o < O) ? b2[o] : 0.f;
+        float s1 = 0.f, s2 = 0.f, y0 = 0.f;
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const int p = pb * 16 + 4 * g + v;
+            const bool ok = p < np && o < O;
+            const float val = acc[pb][og][cb][v] + bias;
+            if (ok) Y[(size_t)(p0 + p) * ldy + o] = val;
+            if (part) {                              // a kernel argument: uniform
+              // shifted sums around the tile's first row of the column (point p0: lane `col`, element 0 of the first fragment)
+              if (pb == 0 && v == 0) y0 = __shfl(val, col);
+              if (ok) {
+                const float d = val - y0;
+                s1 += d;
+                s2 = fmaf(d, d, s2);
+              }
+            }
+          }
+        if (part) {
+          s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);      // the four point groups of a column, in a fixed order
+          s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
+          if (g == 0 && o < O) {
+            float* rec = part + ((size_t)bx * O + o) * 2;
+            rec[0] = fmaf(cnt, y0, s1);
+            rec[1] = fmaxf(s2 - s1 * s1 / cnt, 0.f);
+          }
+        }
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ gradient of the activated edge tensor
+// A[p][o] = dy(p,o), B[o][c] = W2t[(r*F1 + c), o], D[p][c]: 32 points x 128 channels per workgroup pass, no LDS.
+template <bool VEC>
+__global__ __launch_bounds__(256) void edge_rank_dgrad_kernel(const float* __restrict__ G, int ldg, const float* __restrict__ Wt, int ldwt,
+                                                              const float* __restrict__ PQ, int ld, const int32_t* __restrict__ idx, int M, int k,
+                                                              int F1, int O, const float* __restrict__ sc, const float* __restrict__ sh,
+                                                              const float* __restrict__ mean, const float* __restrict__ invstd, float slope,
+                                                              float* __restrict__ dA, float* __restrict__ part) {
+  const int bx = xcd_block();
+  const int p0 = bx * ER_PT;
+  if (p0 >= M) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, g = lane >> 4;
+  for (int cp = 0; cp < F1; cp += 128) {
+    const int cw = cp + wave * 32;
+    if (cw >= F1) continue;
+    float a_[2], s_[2], mu[2], is[2], t1[2] = {0.f, 0.f}, t2[2] = {0.f, 0.f};
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+      const int c = cw + cb * 16 + col;
+      const bool ok = c < F1;
+      a_[cb] = ok ? sc[c] : 0.f; s_[cb] = ok ? sh[c] : 0.f; mu[cb] = ok ? mean[c] : 0.f; is[cb] = ok ? invstd[c] : 0.f;
+    }
+    for (int r = 0; r < k; ++r) {
+      f32x4 acc[2][2];
+      acc[0][0] = acc[0][1] = acc[1][0] = acc[1][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int ob = 0; ob < O; ob += 16) {
+        const int o = ob + 4 * g;
+        f32x4 a[2], b[2];
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb) {
+          const int p = p0 + pb * 16 + col;
+          a[pb] = ld4<VEC>(G + (size_t)min(p, M - 1) * ldg + o, p < M ? O - o : 0);
+        }
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+          const int c = cw + cb * 16 + col;
+          b[cb] = ld4<VEC>(Wt + ((size_t)r * F1 + min(c, F1 - 1)) * ldwt + o, c < F1 ? O - o : 0);
+        }
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb) acc[pb][cb] = mfma4(a[pb], b[cb], acc[pb][cb]);
+      }
+#pragma unroll
+      for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int p = p0 + pb * 16 + 4 * g + v;
+          if (p >= M) continue;
+          const int n = neighbour(idx, p, k, r, M);
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb) {
+            const int c = cw + cb * 16 + col;
+            if (c < F1) {
+              const float q = PQ[(size_t)p * ld + F1 + c], pv = PQ[(size_t)n * ld + c];
+              const float da = acc[pb][cb][v] * lrelu_mask(pre_act(q, pv, a_[cb], s_[cb]), slope);
+              dA[((size_t)p * k + r) * F1 + c] = da;
+              t1[cb] += da;
+              t2[cb] = fmaf(da, ((q + pv) - mu[cb]) * is[cb], t2[cb]);
+            }
+          }
+        }
+    }
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+      float a = t1[cb], b = t2[cb];
+      a += __shfl_xor(a, 16); b += __shfl_xor(b, 16);         // the four point groups of a column, in a fixed order
+      a += __shfl_xor(a, 32); b += __shfl_xor(b, 32);
+      const int c = cw + cb * 16 + col;
+      if (g == 0 && c < F1) {
+        float* rec = part + ((size_t)bx * F1 + c) * 2;
+        rec[0] = a;
+        rec[1] = b;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ weight gradient
+// D[o][c] (one per rank) += A[o][point] B[point][c]: A = dy (global), B = the staged h; an MFMA step reduces over four consecutive points.
+struct RwPlan {
+  int n_ot, n_ct, n_rp, tiles, splits, pps;
+};
+inline RwPlan er_wg_plan(int M, int k, int F1, int O) {
+  RwPlan p;
+  p.n_ot = cdiv(O, 128); p.n_ct = cdiv(F1, ER_CK); p.n_rp = cdiv(k, ER_RB);
+  p.tiles = p.n_ot * p.n_ct * p.n_rp;
+  // about 1024 workgroups: a narrow layer is split over up to 512 point ranges, a wide one over a few
+  int s = cdiv(1024, p.tiles);
+  s = s < 1 ? 1 : (s > 512 ? 512 : s);
+  // the workspace (splits * O * k*F1 floats) stays below a quarter of the backward's [M,k,F1] buffer
+  const int cap = M / (4 * O);
+  s = s > cap ? (cap < 1 ? 1 : cap) : s;
+  p.pps = cdiv(cdiv(M, s), 32) * 32;
+  p.splits = cdiv(M, p.pps);
+  return p;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void edge_rank_wgrad_kernel(const float* __restrict__ PQ, int ld, const int32_t* __restrict__ idx, int M, int k, int F1,
+                                                              const float* __restrict__ sc, const float* __restrict__ sh, float slope,
+                                                              const float* __restrict__ G, int ldg, int O, float* __restrict__ ws, RwPlan pl) {
+  __shared__ __attribute__((aligned(16))) float sm[32 * ER_RB * ER_WPST];
+  const int L = xcd_block();
+  if (L >= pl.tiles * pl.splits) return;
+  const int s = L / pl.tiles, tile = L % pl.tiles;
+  const int ot = tile % pl.n_ot, ct = (tile / pl.n_ot) % pl.n_ct, rp = tile / (pl.n_ot * pl.n_ct);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, g = lane >> 4;
+  const int c0 = ct * ER_CK, r0 = rp * ER_RB, o0 = ot * 128 + wave * 32;
+  const int begin = s * pl.pps, end = min(M, begin + pl.pps);
+  f32x4 acc[2][ER_RB][4];
+#pragma unroll
+  for (int rb = 0; rb < ER_RB; ++rb)
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) acc[0][rb][cb] = acc[1][rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int pb = begin; pb < end; pb += 32) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < 32 * ER_RB * (ER_CK / 4); e += 256) {
+      const int cc = (e & 15) * 4, rb = (e >> 4) % ER_RB, p = e / (16 * ER_RB);
+      const int i = pb + p;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (i < end && r0 + rb < k && c0 + cc < F1) v = rank_h4<VEC>(PQ, ld, F1, i, neighbour(idx, i, k, r0 + rb, M), c0 + cc, sc, sh, slope);
+      *reinterpret_cast<f32x4*>(sm + (p * ER_RB + rb) * ER_WPST + cc) = v;
+    }
+    __syncthreads();
+    if (o0 >= O) continue;
+    for (int q = 0; q < 8; ++q) {
+      if (pb + q * 4 >= end) break;                    // uniform
+      const int pt = q * 4 + g;
+      const int i = pb + pt;
+      float a[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int o = o0 + h * 16 + col;
+        a[h] = (i < end && o < O) ? G[(size_t)i * ldg + o] : 0.f;
+      }
+#pragma unroll
+      for (int rb = 0; rb < ER_RB; ++rb) {
+        if (r0 + rb < k) {
+#pragma unroll
+          for (int cb = 0; cb < 4; ++cb) {
+            const float b = sm[(pt * ER_RB + rb) * ER_WPST + cb * 16 + col];
+            acc[0][rb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b, acc[0][rb][cb], 0, 0, 0);
+            acc[1][rb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b, acc[1][rb][cb], 0, 0, 0);
+          }
+        }
+      }
+    }
+  }
+  const size_t ldw = (size_t)k * F1;
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int rb = 0; rb < ER_RB; ++rb)
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int o = o0 + h * 16 + 4 * g + v, c = c0 + cb * 16 + col;
+          if (r0 + rb < k && o < O && c < F1) ws[((size_t)s * O + o) * ldw + (size_t)(r0 + rb) * F1 + c] = acc[h][rb][cb][v];
+        }
+}
+
+// dW[o, e] = sum_s ws[s][o][e]: eight lanes per element take the splits s = q, q + 8, ... in ascending order and their partial sums are
+// combined in a fixed order (a fixed assignment: run-to-run identical, no float atomics)
+__global__ __launch_bounds__(256) void edge_rank_wgrad_reduce_kernel(const float* __restrict__ ws, int splits, int O, int KW, float* __restrict__ dW,
+                                                                     int lddw) {
+  const size_t t = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 3, n = (size_t)O * KW;
+  const int q = threadIdx.x & 7;
+  float a = 0.f;
+  if (t < n)
+    for (int s = q; s < splits; s += 8) a += ws[(size_t)s * n + t];
+  a += __shfl_xor(a, 1);
+  a += __shfl_xor(a, 2);
+  a += __shfl_xor(a, 4);
+  if (t < n && q == 0) dW[(t / KW) * lddw + (t % KW)] = a;
+}
+
+// ------------------------------------------------------------------------------------------ edge gradients -> point gradients
+// one thread per (point, V channels): dQ over the point's own k edges, dP over its in-edge list in ascending edge order
+template <int V>
+__device__ __forceinline__ void ldv(const float* __restrict__ p, float (&v)[V]) {
+  if constexpr (V == 4) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    v[0] = *p;
+  }
+}
+template <int V>
+__device__ __forceinline__ void stv(float* __restrict__ p, const float (&v)[V]) {
+  if constexpr (V == 4) *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+  else *p = v[0];
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void edge_rank_scatter_kernel(const float* __restrict__ dA, const int32_t* __restrict__ rowptr,
+                                                                const int32_t* __restrict__ src, const float* __restrict__ PQ, int ld,
+                                                                const int32_t* __restrict__ idx, int M, int k, int F1, const float* __restrict__ sc,
+                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                const float* __restrict__ sums, float inv_e, float* __restrict__ dPQ, int ldd) {
+  const int QC = F1 / V;
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (tid >= (size_t)M * QC) return;
+  const int m = (int)(tid / QC), c = (int)(tid % QC) * V;
+  const bool train = sums != nullptr;
+  float a[V], mu[V], is[V], A[V], Bc[V], pm[V], qm[V], dq[V], dp[V], d[V], o[V];
+  ldv<V>(sc + c, a);
+#pragma unroll
+  for (int u = 0; u < V; ++u) mu[u] = is[u] = A[u] = Bc[u] = pm[u] = qm[u] = o[u] = dq[u] = dp[u] = 0.f;
+  if (train) {
+    ldv<V>(mean + c, mu); ldv<V>(invstd + c, is);
+    ldv<V>(sums + c, A); ldv<V>(sums + F1 + c, Bc);
+    ldv<V>(PQ + (size_t)m * ld + c, pm); ldv<V>(PQ + (size_t)m * ld + F1 + c, qm);
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+      A[u] *= inv_e; Bc[u] *= inv_e;
+    }
+  }
+  for (int r = 0; r < k; ++r) {
+    ldv<V>(dA + ((size_t)m * k + r) * F1 + c, d);
+    if (train) ldv<V>(PQ + (size_t)neighbour(idx, m, k, r, M) * ld + c, o);
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+      float dz = d[u];
+      if (train) dz = dz - A[u] - (((qm[u] + o[u]) - mu[u]) * is[u]) * Bc[u];
+      dq[u] += a[u] * dz;
+    }
+  }
+  const int t0 = rowptr[m], t1 = rowptr[m + 1];
+  for (int t = t0; t < t1; ++t) {            // ascending edge ids: a fixed summation order
+    const int e = src[t];
+    ldv<V>(dA + (size_t)e * F1 + c, d);
+    if (train) ldv<V>(PQ + (size_t)(e / k) * ld + F1 + c, o);
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+      float dz = d[u];
+      if (train) dz = dz - A[u] - (((o[u] + pm[u]) - mu[u]) * is[u]) * Bc[u];
+      dp[u] += a[u] * dz;
+    }
+  }
+  stv<V>(dPQ + (size_t)m * ldd + c, dp);
+  stv<V>(dPQ + (size_t)m * ldd + F1 + c, dq);
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool sizes_ok(int M, int k, int F1, int O) {
+  return M > 0 && k >= 1 && k <= ER_KMAX && F1 > 0 && O > 0 && (long)M * k <= 0x7fffffffL && (long)k * F1 <= 0x7fffffffL;
+}
+
+}  // namespace
+
+extern "C" int spgan_edge_rank_tile_points(int k) {
+  if (k < 1 || k > ER_KMAX) return 0;
+  return ER_PT;
+}
+
+extern "C" int spgan_edge_rank_gemm(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1,
+                                    float slope, const float* W2i, int ldw, const float* b2, int O, float* Y, int ldy, float* partials,
+                                    spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(PQ && idx && scale1 && shift1 && W2i && Y && sizes_ok(M, k, F1, O) && ld >= 2 * F1 && ldw >= k * F1 && ldy >= O);
+  const bool vec = F1 % 4 == 0 && ld % 4 == 0 && ldw % 4 == 0 && al16(PQ) && al16(W2i) && al16(scale1) && al16(shift1);
+  const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
+  hipStream_t st = (hipStream_t)s_;
+  if (vec) hipLaunchKernelGGL(edge_rank_gemm_kernel<true>, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials);
+  else hipLaunchKernelGGL(edge_rank_gemm_kernel<false>, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials);
+  return spgan_launch_status();
+}
+
+extern "C" size_t spgan_edge_rank_wgrad_ws_bytes(int M, int k, int F1, int O) {
+  if (!sizes_ok(M, k, F1, O)) return 0;
+  return (size_t)er_wg_plan(M, k, F1, O).splits * O * k * F1 * sizeof(float);
+}
+
+extern "C" int spgan_edge_rank_wgrad(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1,
+                                     float slope, const float* dY, int ldg, int O, float* dW2i, int lddw, float* ws, size_t ws_bytes,
+                                     spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(PQ && idx && scale1 && shift1 && dY && dW2i && ws && sizes_ok(M, k, F1, O) && ld >= 2 * F1 && ldg >= O && lddw >= k * F1);
+  SPGAN_CHECK_ARG(ws_bytes >= spgan_edge_rank_wgrad_ws_bytes(M, k, F1, O));
+  const RwPlan pl = er_wg_plan(M, k, F1, O);
+  const bool vec = F1 % 4 == 0 && ld % 4 == 0 && al16(PQ) && al16(scale1) && al16(shift1);
+  const dim3 gr(grid8((long)pl.tiles * pl.splits)), b(256);
+  hipStream_t st = (hipStream_t)s_;
+  if (vec) hipLaunchKernelGGL(edge_rank_wgrad_kernel<true>, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl);
+  else hipLaunchKernelGGL(edge_rank_wgrad_kernel<false>, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl);
+  int e = spgan_launch_status();
+  if (e) return e;
+  hipLaunchKernelGGL(edge_rank_wgrad_reduce_kernel, dim3(cdiv((long)O * k * F1 * 8, 256)), dim3(256), 0, st, ws, pl.splits, O, k * F1, dW2i, lddw);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_edge_rank_dgrad(const float* dY, int ldg, const float* W2t, int ldwt, const float* PQ, int ld, const int32_t* idx, int M, int k,
+                                     int F1, int O, const float* scale1, const float* shift1, const float* mean1, const float* invstd1, float slope,
+                                     float* dA, float* partials, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(dY && W2t && PQ && idx && scale1 && shift1 && mean1 && invstd1 && dA && partials && sizes_ok(M, k, F1, O));
+  SPGAN_CHECK_ARG(ldg >= O && ldwt >= O && ld >= 2 * F1);
+  const bool vec = O % 4 == 0 && ldg % 4 == 0 && ldwt % 4 == 0 && al16(dY) && al16(W2t);
+  const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
+  hipStream_t st = (hipStream_t)s_;
+  if (vec)
+    hipLaunchKernelGGL(edge_rank_dgrad_kernel<true>, gr, b, 0, st, dY, ldg, W2t, ldwt, PQ, ld, idx, M, k, F1, O, scale1, shift1, mean1, invstd1, slope, dA,
+                       partials);
+  else
+    hipLaunchKernelGGL(edge_rank_dgrad_kernel<false>, gr, b, 0, st, dY, ldg, W2t, ldwt, PQ, ld, idx, M, k, F1, O, scale1, shift1, mean1, invstd1, slope, dA,
+                       partials);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_edge_rank_scatter(const float* dA, const int32_t* rowptr, const int32_t* src, const float* PQ, int ld, const int32_t* idx, int M,
+                                       int k, int F1, const float* scale1, const float* mean1, const float* invstd1, const float* sums, float* dPQ,
+                                       int ldd, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(dA && rowptr && src && scale1 && dPQ && sizes_ok(M, k, F1, 1) && ldd >= 2 * F1);
+  if (sums) SPGAN_CHECK_ARG(PQ && idx && mean1 && invstd1 && ld >= 2 * F1);
+  const float inv_e = 1.0f / ((float)M * (float)k);
+  const bool v4 = F1 % 4 == 0 && ldd % 4 == 0 && al16(dA) && al16(dPQ) && al16(scale1) &&
+                  (!sums || (ld % 4 == 0 && al16(PQ) && al16(mean1) && al16(invstd1) && al16(sums)));
+  const long items = (long)M * (v4 ? F1 / 4 : F1);
+  hipStream_t st = (hipStream_t)s_;
+  if (v4)
+    hipLaunchKernelGGL(edge_rank_scatter_kernel<4>, dim3(cdiv(items, 256)), dim3(256), 0, st, dA, rowptr, src, PQ, ld, idx, M, k, F1, scale1, mean1,
+                       invstd1, sums, inv_e, dPQ, ldd);
+  else
+    hipLaunchKernelGGL(edge_rank_scatter_kernel<1>, dim3(cdiv(items, 256)), dim3(256), 0, st, dA, rowptr, src, PQ, ld, idx, M, k, F1, scale1, mean1,
+                       invstd1, sums, inv_e, dPQ, ldd);
+  return spgan_launch_status();
+}

@@ -289,6 +289,12 @@ SIGNATURES = {
     "spgan_edge_window_wgrad": (I, [P, I, P, I, I, I, P, I, I, I, P, I, P, SZ, P]),
     "spgan_edge_window_dgrad": (I, [P, I, P, I, I, I, I, I, I, P, I, P]),
     "spgan_edge_window_scatter": (I, [P, P, P, I, I, I, P, I, P, I, P, I, P]),
+    "spgan_edge_rank_tile_points": (I, [I]),
+    "spgan_edge_rank_gemm": (I, [P, I, P, I, I, I, P, P, F, P, I, P, I, P, I, P, P]),
+    "spgan_edge_rank_wgrad_ws_bytes": (SZ, [I, I, I, I]),
+    "spgan_edge_rank_wgrad": (I, [P, I, P, I, I, I, P, P, F, P, I, I, P, I, P, SZ, P]),
+    "spgan_edge_rank_dgrad": (I, [P, I, P, I, P, I, P, I, I, I, I, P, P, P, P, F, P, P, P]),
+    "spgan_edge_rank_scatter": (I, [P, P, P, P, I, P, I, I, I, P, P, P, P, P, I, P]),
     "spgan_nn_distance": (I, [P, P, I, I, I, P, P, P]),
     "spgan_chamfer_bwd": (I, [P, P, I, I, I, P, P, P, P, P, P]),
     "spgan_chamfer_pairs": (I, [P, P, I, I, I, I, P, P]),

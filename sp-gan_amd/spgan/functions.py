@@ -15,7 +15,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import edge_max, edge_window, nets, ops
+from . import edge_max, edge_rank, edge_window, nets, ops
 
 Tensor = torch.Tensor
 
@@ -758,6 +758,124 @@ class UpsampleEdgeConvFn(Function):
             db2 = torch.zeros(F2, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dy)[0]
         return (None, dx, dW1, db1, sums1[4 * C:].clone() if need[4] else None, sums1[:4 * C].clone() if need[5] else None,
                 dV, db2, sums2[F2:].clone() if need[8] else None, sums2[:F2].clone() if need[9] else None)
+
+
+_RANK_IMAGES: Dict[tuple, tuple] = {}
+
+
+def rank_images(W1: Tensor, W2: Tensor):
+    """The operand images of the full-rank edge convolution's two conv weights (W1 [F1,2Fin,1,1], W2 [Fout,F1,1,k]):
+    (Wst [2F1,Fin] = [Wd ; Wc - Wd] (rows of P, then of Q), Wst^T, W2i [Fout, k*F1] tap-major (column r*F1 + c), W2i^T).
+    Cached per weight pair under the staleness rule of upsample_images; inside a capture the images are rebuilt."""
+    def build():
+        F1, Fin = W1.shape[0], W1.shape[1] // 2
+        Wm = W1.reshape(F1, 2 * Fin)
+        Wd = Wm[:, Fin:]
+        Wst = torch.cat([Wd, Wm[:, :Fin] - Wd], dim=0)
+        W2i = W2[:, :, 0, :].permute(0, 2, 1).reshape(W2.shape[0], W2.shape[3] * F1)
+        return Wst, Wst.t().contiguous(), W2i, W2i.t().contiguous()
+    W1, W2 = W1.detach(), W2.detach()
+    if ops.capturing():
+        return build()
+    key = (W1.data_ptr(), W2.data_ptr(), tuple(W1.shape), tuple(W2.shape))
+    stamp = (ops.weights_epoch_of(W1), ops.weights_epoch_of(W2), W1._version, W2._version)
+    hit = _RANK_IMAGES.get(key)
+    if hit is not None and hit[0] == stamp:
+        return hit[1]
+    if len(_RANK_IMAGES) >= 64:
+        _RANK_IMAGES.clear()
+    img = build()
+    _RANK_IMAGES[key] = (stamp, img)
+    return img
+
+
+class RankEdgeConvFn(Function):
+    """out [B,Fout,N] = relu(bn2(conv[1,k](lrelu(bn1(conv1x1(cat[x_i, x_j - x_i]))))))   (the reference's deform_edgeConv_simple /
+    deform_edgeConv_first, Generation/modules.py:1394-1466) without the [B,2Fin,N,k] edge tensor or the activated [B,F1,N,k] tensor in
+    forward: one per-point GEMM PQ = x.[Wd ; Wc - Wd]^T + [0 ; b1], the first BatchNorm's statistics from edge_max's gather pass over PQ, and
+    the [1,k] convolution as a product with K = k*F1 whose A operand is formed in LDS (csrc/edge_rank.hip).
+    inputs: holder(B, N, k, training, idx | None, knn_mode, slope, bn1, bn2 = the nn.BatchNorm2d modules), x [B,Fin,N], then
+    inte_conv_hk's conv weight, conv bias, bn weight, bn bias and conv2's.  Saved: x, PQ, the pre-norm y [M,Fout], the graph and the
+    statistics; the backward holds one per-edge buffer, da [M,k,F1].  Once differentiable, as EdgeMaxConvFn."""
+
+    @staticmethod
+    def forward(ctx, h, x, W1, b1, g1, be1, W2, b2, g2, be2):
+        B, Fin, N = x.shape
+        k, M = h.k, B * N
+        bn1, bn2 = h.bn1, h.bn2
+        x_pm = ops.cm_to_pm(x)
+        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
+        Wst, _, W2i, _ = rank_images(W1, W2)
+        PQ = ops.gemm_nt(x_pm, Wst, torch.cat([torch.zeros_like(b1), b1]))
+        if h.training:
+            # the (sum, M2) records of Q_i + P_j over the M*k edges come from edge_max's gather pass; its max / min outputs are dropped
+            part = edge_max.edge_max_gather(PQ, idx)[4:]
+            st1 = edge_max.edge_max_bn(part[0], part[1], M * k, g1, be1, bn1.running_mean, bn1.running_var, float(bn1.momentum), float(bn1.eps))
+            bn1.num_batches_tracked += 1
+            Y, part, rows = edge_rank.edge_rank_gemm(PQ, idx, st1[0], st1[1], W2i, b2, stats=True, slope=h.slope)
+            st2 = edge_max.edge_max_bn(part, rows, M, g2, be2, bn2.running_mean, bn2.running_var, float(bn2.momentum), float(bn2.eps))
+            bn2.num_batches_tracked += 1
+            del part
+        else:
+            st1 = ops.bn_prepare(None, None, g1, be1, M * k, False, bn1.running_mean, bn1.running_var, eps=float(bn1.eps))
+            Y = edge_rank.edge_rank_gemm(PQ, idx, st1[0], st1[1], W2i, b2, slope=h.slope)
+            st2 = ops.bn_prepare(None, None, g2, be2, M, False, bn2.running_mean, bn2.running_var, eps=float(bn2.eps))
+        out_pm = ops.affine_act(Y, st2[0], st2[1], 0.0)
+        h.last_idx = idx
+        # the statistics are made here and handed to nobody else: they ride on ctx (see EdgeMaxConvFn)
+        ctx.h, ctx.st1, ctx.st2 = h, tuple(st1[i] for i in range(4)), tuple(st2[i] for i in range(4))
+        ctx.save_for_backward(x, PQ, Y, idx, W1, W2, g2)
+        return ops.pm_to_cm(out_pm, B, N)
+
+    @staticmethod
+    def backward(ctx, dout):
+        if torch.is_grad_enabled():
+            raise RuntimeError("deform_edgeConv is once differentiable: its backward was asked to build a graph (create_graph=True), but "
+                               "it has no double backward -- the layer cannot sit under a gradient penalty")
+        return RankEdgeConvFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        from . import pointnet_util
+        x, PQ, Y, idx, W1, W2, g2 = ctx.saved_tensors
+        h = ctx.h
+        B, Fin, N = x.shape
+        k, M = h.k, B * N
+        F1, Fout = W1.shape[0], W2.shape[0]
+        sc1, sh1, inv1, mu1 = ctx.st1
+        sc2, sh2, inv2, mu2 = ctx.st2
+        need = ctx.needs_input_grad
+        Wst, Wstt, W2i, W2t = rank_images(W1, W2)
+        # ReLU + BatchNorm of conv2
+        g = ops.cm_to_pm(dout.contiguous())
+        r, sums2 = pointnet_util._group_max_bwd(g, ops.affine_act(Y, sc2, sh2, 0.0), None, Y, mu2, inv2, 0.0, 1)
+        dy = ops.bn_bwd_apply(r, Y, mu2, inv2, g2, sums2 if h.training else torch.zeros_like(sums2), M)
+        del g, r
+        # LeakyReLU + BatchNorm of inte_conv_hk: da [M,k,F1] is the only per-edge tensor of the layer
+        da, sums1 = edge_rank.edge_rank_dgrad(dy, W2t, PQ, idx, sc1, sh1, mu1, inv1, h.slope)
+        rowptr, src = ops.csr_build(idx, B, N)
+        if h.training:
+            dPQ = edge_rank.edge_rank_scatter(da, rowptr, src, sc1, PQ, idx, mu1, inv1, sums1)
+        else:
+            dPQ = edge_rank.edge_rank_scatter(da, rowptr, src, sc1)
+        del da
+        dW2 = None
+        if need[6]:                                                      # after da has died: its split workspace is not held beside da
+            dW2 = edge_rank.edge_rank_wgrad(PQ, idx, sc1, sh1, dy, h.slope).view(Fout, k, F1).permute(0, 2, 1).unsqueeze(2).contiguous()
+        dW1 = None
+        if need[2]:
+            dWst = ops.gemm_tn(dPQ, ops.cm_to_pm(x))                     # [2F1, Fin]: rows of dW'_P, then of dW'_Q
+            dW1 = torch.cat([dWst[F1:], dWst[:F1] - dWst[F1:]], dim=1).view(F1, 2 * Fin, 1, 1)      # dWc = dW'_Q, dWd = dW'_P - dW'_Q
+        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wstt), B, N) if need[1] else None
+        # a bias in front of a train-mode BatchNorm: exactly zero (the batch mean absorbs it)
+        db1 = db2 = None
+        if need[3]:
+            db1 = torch.zeros(F1, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dPQ[:, F1:])[0]
+        if need[7]:
+            db2 = torch.zeros(Fout, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dy)[0]
+        return (None, dx, dW1, db1, sums1[F1:].clone() if need[4] else None, sums1[:F1].clone() if need[5] else None,
+                dW2, db2, sums2[Fout:].clone() if need[8] else None, sums2[:Fout].clone() if need[9] else None)
 
 
 class EdgeFeaturesFn(Function):

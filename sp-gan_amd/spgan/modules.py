@@ -739,3 +739,84 @@ class upsample_edgeConv(nn.Module):
                                           self.conv2.conv.weight, self.conv2.conv.bias, bn2.weight, bn2.bias)
         self.last_idx = h.last_idx
         return out
+
+
+class _RankEdgeConv(nn.Module):
+    """The shared body of deform_edgeConv_simple / deform_edgeConv_first: conv2(inte_conv_hk(get_edge_features(x))) with
+    inte_conv_hk = Conv2d(2Fin -> F1, 1x1) + BatchNorm2d + LeakyReLU and conv2 = conv2dbr(F1 -> Fout, [1,k]), evaluated over gathered rows
+    of one per-point GEMM (Fn.RankEdgeConvFn, csrc/edge_rank.hip): neither the [B,2Fin,N,k] edge tensor nor the activated [B,F1,N,k]
+    tensor exists in forward; the backward holds one [B*N,k,F1] buffer.  The sub-modules are parameter containers with the reference's
+    names (state_dicts load strictly both ways); conv2 on its own still refuses its [1,k] kernel for k > 1."""
+
+    def __init__(self, Fin, F1, Fout, k):
+        super().__init__()
+        name = type(self).__name__
+        if not 1 <= k <= 32:
+            raise ValueError("%s: k must lie in 1..32, got k=%d (Fin=%d, Fout=%d)" % (name, k, Fin, Fout))
+        if Fin < 1 or Fout < 1:
+            raise ValueError("%s: Fin and Fout must be positive, got Fin=%d, Fout=%d" % (name, Fin, Fout))
+        self.k = k
+        self.Fin = Fin
+        self.Fout = Fout
+        self.conv2 = conv2dbr(F1, Fout, [1, k], [1, 1])
+        self.inte_conv_hk = nn.Sequential(
+            nn.Conv2d(2 * Fin, F1, [1, 1], [1, 1]),
+            nn.BatchNorm2d(F1),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.last_idx: Optional[torch.Tensor] = None
+
+    def _run(self, x, idx):
+        name = type(self).__name__
+        _require_gpu(x, name)
+        B, Fin, N = x.shape
+        if Fin != self.Fin:
+            raise ValueError("%s(%d, %d, %d) got an input with %d channels" % (name, self.Fin, self.Fout, self.k, Fin))
+        conv1, bn1, act = self.inte_conv_hk[0], self.inte_conv_hk[1], self.inte_conv_hk[2]
+        bn2 = self.conv2.bn
+        for bn in (bn1, bn2):
+            if bn.momentum is None or not bn.track_running_stats:
+                raise NotImplementedError("%s: BatchNorm2d with momentum=None or track_running_stats=False is not supported" % name)
+        if idx is not None:
+            _require_gpu(idx, name + " idx")
+            if idx.dtype == torch.int64:
+                if idx.numel() != B * N * self.k:
+                    raise ValueError("%s: idx must hold B*N*k = %d indices, got %s" % (name, B * N * self.k, tuple(idx.shape)))
+                if not ops.capturing() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+                    raise IndexError("%s: a neighbour index lies outside [0, %d)" % (name, N))
+                idx = ops.idx_from_local64(idx.reshape(B, N * self.k), B, N, self.k)
+            elif idx.dtype != torch.int32 or tuple(idx.shape) != (B * N, self.k):
+                raise ValueError("%s: idx must be int64 [B, N*k] (local) or int32 [B*N, k] (global rows)" % name)
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=1 if Fin <= 4 else 0, slope=float(act.negative_slope),
+                    bn1=bn1, bn2=bn2, last_idx=None)
+        out = Fn.RankEdgeConvFn.apply(h, x.contiguous(), conv1.weight, conv1.bias, bn1.weight, bn1.bias,
+                                      self.conv2.conv.weight, self.conv2.conv.bias, bn2.weight, bn2.bias)
+        self.last_idx = h.last_idx
+        return out
+
+
+class deform_edgeConv_simple(_RankEdgeConv):
+    """Generation/modules.py:1432-1466: [B,Fin,N] -> [B,Fout,N], Conv2d(2Fin -> Fout, 1x1) + BatchNorm2d + LeakyReLU over the edge features,
+    then conv2dbr(Fout -> Fout, [1,k]) over the k neighbour ranks.  pc is accepted and unused, as in the reference.  idx (an extension, as
+    edgeConv's): the graph to use instead of the kNN graph of x, int64 [B, N*k] local indices (range-checked outside a capture) or int32
+    [B*N,k] global rows (trusted).  1 <= k <= 32.  Once differentiable.  last_idx: the graph of the latest forward."""
+
+    def __init__(self, Fin, Fout, k):
+        super().__init__(Fin, Fout, Fout, k)
+
+    def forward(self, x, pc=None, idx: Optional[torch.Tensor] = None):
+        return self._run(x, idx)
+
+
+class deform_edgeConv_first(_RankEdgeConv):
+    """Generation/modules.py:1394-1428: Conv2d(2Fin -> Fin, 1x1) + BatchNorm2d + LeakyReLU over the edge features, then
+    conv2dbr(Fin -> Fout, [1,k]) over the k neighbour ranks.  The result has the reference's literal shape [B,Fout,N,1,1]: the reference
+    applies `unsqueeze(3)` to its [B,Fout,N,1] tensor where deform_edgeConv_simple squeezes; this is the reference's behaviour, kept so
+    that swapped imports see the same shapes, and `.view(B, Fout, N)` of the result is free.  idx, k and last_idx as deform_edgeConv_simple."""
+
+    def __init__(self, Fin, Fout, k):
+        super().__init__(Fin, Fin, Fout, k)
+
+    def forward(self, x, idx: Optional[torch.Tensor] = None):
+        out = self._run(x, idx)
+        return out.view(out.shape[0], out.shape[1], out.shape[2], 1, 1)
