@@ -754,6 +754,33 @@ int spgan_edge_rank_dgrad(const float* dY, int ldg, const float* W2t, int ldwt, 
 int spgan_edge_rank_scatter(const float* dA, const int32_t* rowptr, const int32_t* src, const float* PQ, int ld, const int32_t* idx, int M, int k,
                             int F1, const float* scale1, const float* mean1, const float* invstd1, const float* sums, float* dPQ, int ldd,
                             spgan_stream_t s);
+/* Weighted full-rank edge convolution (csrc/edge_rank.hip): the core of deform_edgeConv_feat (Generation/modules.py:1543-1599).  The activated
+ * edge tensor h of the layer above is multiplied by a per-edge, per-channel weight s before the [1,k] convolution:
+ *   a3(i,r,c) = lrelu(scale3[c] * z3[i,r,c] + shift3[c], slope),   z3 [M,k,F1] contiguous = the stored pre-norm output of the weight MLP;
+ *   s = exp(a3 - wmax[i,c]) * wrs[i,c]  (the softmax over the k ranks; wmax, wrs [M,F1] from spgan_edge_weight_norm), or s = a3 when
+ *   wmax == wrs == NULL (softmax=False).  h, s and h*s are formed inside the kernels, never stored.  1 <= k <= 32, any M, F1, O.
+ *   spgan_edge_weight_gather: Z[(i*k + r), c] = Q[i,c] + P[idx[i,r],c]   (Z [M*k, F] contiguous: the pre-norm rows of a narrow edge layer).
+ *   spgan_edge_weight_norm:   wmax[i,c] = max_r a3(i,r,c), wrs[i,c] = 1 / sum_r exp(a3(i,r,c) - wmax[i,c]), ranks in ascending order.
+ *   spgan_edge_weight_gemm:   spgan_edge_rank_gemm with h * s in place of h (same tiling, partials and finalize).
+ *   spgan_edge_weight_wgrad:  spgan_edge_rank_wgrad with h * s in place of h (workspace: spgan_edge_rank_wgrad_ws_bytes).
+ *   spgan_edge_weight_dgrad:  dm = dY W2i per (point, rank, channel) as spgan_edge_rank_dgrad forms it, then
+ *                               dU[i,r,c] = lrelu'(a_h) * dm * s                        partials_u: (sum dU, sum dU * uhat), uhat = (Q + P - mean1) * invstd1
+ *                               G3[i,r,c] = lrelu'(a3) * s * (dm*h - sum_r' dm*h*s)     partials_3: (sum G3, sum G3 * z3hat), z3hat = (z3 - mean3) * invstd3
+ *                             (softmax=False: G3 = lrelu'(a3) * dm*h).  dU, G3 [M,k,F1] contiguous and distinct; both partials
+ *                             [ceil(M / tile_points)][F1][2] plain sums (finalize mode 1).  No float atomics: results repeat bit for bit. */
+int spgan_edge_weight_gather(const float* PQ, int ld, const int32_t* idx, int M, int k, int F, float* Z, spgan_stream_t s);
+int spgan_edge_weight_norm(const float* z3, int M, int k, int F1, const float* scale3, const float* shift3, float slope, float* wmax, float* wrs,
+                           spgan_stream_t s);
+int spgan_edge_weight_gemm(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1, float slope,
+                           const float* z3, const float* scale3, const float* shift3, const float* wmax, const float* wrs, const float* W2i, int ldw,
+                           const float* b2, int O, float* Y, int ldy, float* partials, spgan_stream_t s);
+int spgan_edge_weight_wgrad(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1, float slope,
+                            const float* z3, const float* scale3, const float* shift3, const float* wmax, const float* wrs, const float* dY, int ldg,
+                            int O, float* dW2i, int lddw, float* ws, size_t ws_bytes, spgan_stream_t s);
+int spgan_edge_weight_dgrad(const float* dY, int ldg, const float* W2t, int ldwt, const float* PQ, int ld, const int32_t* idx, int M, int k, int F1,
+                            int O, const float* scale1, const float* shift1, const float* mean1, const float* invstd1, float slope, const float* z3,
+                            const float* scale3, const float* shift3, const float* mean3, const float* invstd3, const float* wmax, const float* wrs,
+                            float* dU, float* G3, float* partials_u, float* partials_3, spgan_stream_t s);
 /* Per-channel scalar algebra of the double backward, one launch each:
  *   coeffs out4C = [dgammaA | sbarA | xsum0 | xsum1];  phaseb: sums2C = [xsum0+gamma*s0 | xsum1+gamma*s1+invstd*sbarA], dgamma = dgammaA+s1 */
 int spgan_bn_dbl_coeffs(const float* U0, const float* U1, const float* Ugz, const float* S0, const float* S1, const float* gamma,

@@ -20,6 +20,11 @@
 //                            scale1 * da (eval); dQ_i = sum_r dz(i,r), dP_j = sum over the in-edge list of j (spgan_csr_build) in
 //                            ascending edge order.  No float atomics anywhere.
 //
+// The weighted layer (deform_edgeConv_feat, Generation/modules.py:1543-1599) multiplies h by a per-edge weight s before the [1,k] convolution
+// (WMod below).  spgan_edge_weight_gemm / _wgrad are the gemm / wgrad kernels staging h * s; spgan_edge_weight_dgrad turns dm = dy W2i into
+// the gradients reaching both pre-activation BatchNorm outputs (du, g3) with their column records; spgan_edge_weight_norm writes the
+// softmax normaliser per (point, channel) and spgan_edge_weight_gather the pre-norm rows of the weight MLP's first layer.
+//
 // MFMA operand order as in edge_window.hip: a 16-wide K block is one 16-byte fragment per lane (lane group g = lane>>4 holds K elements
 // 4g..4g+3), consumed by four MFMA steps; A and B agree on that order.  fp32 operands, fp32 accumulation: exact products.
 #include "common.hpp"
@@ -84,14 +89,39 @@ __device__ __forceinline__ f32x4 rank_h4(const float* __restrict__ PQ, int ld, i
   return h;
 }
 
+// The per-edge weight of the weighted layers (deform_edgeConv_feat): s(i,r,c) = softmax over r of a3 = lrelu(sc3 * z3 + sh3) with
+// z3 [M,k,F1] the stored pre-norm output of the weight MLP, evaluated from the per-(point, channel) normaliser wmax = max_r a3 and
+// wrs = 1 / sum_r exp(a3 - wmax) (spgan_edge_weight_norm); wmax == nullptr: s = a3 (softmax=False).  Every kernel forms s with
+// weight_s(), so that forward and backward agree bit for bit.
+struct WMod {
+  const float* z3; const float* sc3; const float* sh3; const float* wmax; const float* wrs;
+};
+__device__ __forceinline__ float weight_s(float a3, float mx, float rs, bool soft) { return soft ? expf(a3 - mx) * rs : a3; }
+
+template <bool VEC>
+__device__ __forceinline__ f32x4 weight_s4(const WMod& m, int F1, int k, int i, int r, int c, float slope) {
+  const int nv = F1 - c;
+  const f32x4 z = ld4<VEC>(m.z3 + ((size_t)i * k + r) * F1 + c, nv), a = ld4<VEC>(m.sc3 + c, nv), b = ld4<VEC>(m.sh3 + c, nv);
+  const bool soft = m.wmax != nullptr;
+  f32x4 mx = {0.f, 0.f, 0.f, 0.f}, rs = mx, s;
+  if (soft) {
+    mx = ld4<VEC>(m.wmax + (size_t)i * F1 + c, nv);
+    rs = ld4<VEC>(m.wrs + (size_t)i * F1 + c, nv);
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) s[u] = weight_s(lrelu_f(fmaf(a[u], z[u], b[u]), slope), mx[u], rs[u], soft);
+  return s;
+}
+
 // ------------------------------------------------------------------------------------------ forward
 // Per wave: 2 blocks of 16 points x (2 groups of 128 columns) x 2 blocks of 16 output columns; the four waves of a workgroup take 128
 // consecutive output columns of each group, so one staging serves 256 output columns.
-template <bool VEC>
+// MOD: the staged operand is h * s (WMod above): spgan_edge_weight_gemm.
+template <bool VEC, bool MOD>
 __global__ __launch_bounds__(256, 2) void edge_rank_gemm_kernel(const float* __restrict__ PQ, int ld, const int32_t* __restrict__ idx, int M, int k,
                                                                 int F1, const float* __restrict__ sc, const float* __restrict__ sh, float slope,
                                                                 const float* __restrict__ W, int ldw, const float* __restrict__ b2, int O,
-                                                                float* __restrict__ Y, int ldy, float* __restrict__ part) {
+                                                                float* __restrict__ Y, int ldy, float* __restrict__ part, WMod md) {
   __shared__ __attribute__((aligned(16))) float sm[ER_RS * ER_PT * ER_PST];
   const int bx = xcd_block();
   const int p0 = bx * ER_PT;
@@ -118,6 +148,7 @@ __global__ __launch_bounds__(256, 2) void edge_rank_gemm_kernel(const float* __r
           if (p < np && c0 + cc < F1) {
             const int i = p0 + p;
             v = rank_h4<VEC>(PQ, ld, F1, i, neighbour(idx, i, k, r0 + rs, M), c0 + cc, sc, sh, slope);
+            if constexpr (MOD) v *= weight_s4<VEC>(md, F1, k, i, r0 + rs, c0 + cc, slope);
           }
           *reinterpret_cast<f32x4*>(sm + (rs * ER_PT + p) * ER_PST + cc) = v;
         }
@@ -286,10 +317,10 @@ inline RwPlan er_wg_plan(int M, int k, int F1, int O) {
   return p;
 }
 
-template <bool VEC>
+template <bool VEC, bool MOD>
 __global__ __launch_bounds__(256) void edge_rank_wgrad_kernel(const float* __restrict__ PQ, int ld, const int32_t* __restrict__ idx, int M, int k, int F1,
                                                               const float* __restrict__ sc, const float* __restrict__ sh, float slope,
-                                                              const float* __restrict__ G, int ldg, int O, float* __restrict__ ws, RwPlan pl) {
+                                                              const float* __restrict__ G, int ldg, int O, float* __restrict__ ws, RwPlan pl, WMod md) {
   __shared__ __attribute__((aligned(16))) float sm[32 * ER_RB * ER_WPST];
   const int L = xcd_block();
   if (L >= pl.tiles * pl.splits) return;
@@ -310,7 +341,10 @@ __global__ __launch_bounds__(256) void edge_rank_wgrad_kernel(const float* __res
       const int cc = (e & 15) * 4, rb = (e >> 4) % ER_RB, p = e / (16 * ER_RB);
       const int i = pb + p;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (i < end && r0 + rb < k && c0 + cc < F1) v = rank_h4<VEC>(PQ, ld, F1, i, neighbour(idx, i, k, r0 + rb, M), c0 + cc, sc, sh, slope);
+      if (i < end && r0 + rb < k && c0 + cc < F1) {
+        v = rank_h4<VEC>(PQ, ld, F1, i, neighbour(idx, i, k, r0 + rb, M), c0 + cc, sc, sh, slope);
+        if constexpr (MOD) v *= weight_s4<VEC>(md, F1, k, i, r0 + rb, c0 + cc, slope);
+      }
       *reinterpret_cast<f32x4*>(sm + (p * ER_RB + rb) * ER_WPST + cc) = v;
     }
     __syncthreads();
@@ -434,6 +468,155 @@ __global__ __launch_bounds__(256) void edge_rank_scatter_kernel(const float* __r
   stv<V>(dPQ + (size_t)m * ldd + F1 + c, dq);
 }
 
+// ------------------------------------------------------------------------------------------ the weighted layer's own passes
+// z(i,r,c) = Q_i + P_n(i,r) written out [M*k, F]: the narrow first layer of the weight MLP (F = 16), the rows of the products that follow
+__global__ __launch_bounds__(256) void edge_weight_gather_kernel(const float* __restrict__ PQ, int ld, const int32_t* __restrict__ idx, int M, int k, int F,
+                                                                 float* __restrict__ Z) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (tid >= (size_t)M * k * F) return;
+  const int c = (int)(tid % F);
+  const size_t e = tid / F;
+  const int i = (int)(e / k), r = (int)(e % k);
+  Z[tid] = PQ[(size_t)i * ld + F + c] + PQ[(size_t)neighbour(idx, i, k, r, M) * ld + c];
+}
+
+// one thread per (point, channel): the softmax normaliser over the k ranks, in ascending rank order
+__global__ __launch_bounds__(256) void edge_weight_norm_kernel(const float* __restrict__ z3, int M, int k, int F1, const float* __restrict__ sc3,
+                                                               const float* __restrict__ sh3, float slope, float* __restrict__ wmax,
+                                                               float* __restrict__ wrs) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (tid >= (size_t)M * F1) return;
+  const int c = (int)(tid % F1);
+  const float* z = z3 + (tid / F1) * (size_t)k * F1 + c;
+  const float a = sc3[c], b = sh3[c];
+  float mx = -INFINITY, sum = 0.f;
+  for (int r = 0; r < k; ++r) mx = fmaxf(mx, lrelu_f(fmaf(a, z[(size_t)r * F1], b), slope));
+  for (int r = 0; r < k; ++r) sum += expf(lrelu_f(fmaf(a, z[(size_t)r * F1], b), slope) - mx);
+  wmax[tid] = mx;
+  wrs[tid] = 1.f / sum;
+}
+
+// dm(p,r,c) = sum_o dy[p,o] W2t[r*F1 + c, o] as edge_rank_dgrad_kernel forms it (the same tiling: a lane owns all k ranks of its
+// (point, channel) pairs), then with h and s recomputed
+//   du = lrelu'(a_h) * dm * s                                  records (sum du, sum du * uhat)
+//   g3 = lrelu'(a_3) * s * (dm*h - t),  t = sum_r dm*h*s       records (sum g3, sum g3 * z3hat)        (softmax; else g3 = lrelu'(a_3) * dm*h)
+// t needs every rank: pass 0 parks dm in dU and accumulates t in registers, pass 1 reads the lane's own dm back and writes du over it.
+template <bool VEC>
+__global__ __launch_bounds__(256) void edge_weight_dgrad_kernel(const float* __restrict__ G, int ldg, const float* __restrict__ Wt, int ldwt,
+                                                                const float* __restrict__ PQ, int ld, const int32_t* __restrict__ idx, int M, int k,
+                                                                int F1, int O, const float* __restrict__ sc, const float* __restrict__ sh,
+                                                                const float* __restrict__ mean, const float* __restrict__ invstd, float slope,
+                                                                WMod md, const float* __restrict__ mean3, const float* __restrict__ invstd3,
+                                                                float* dU, float* __restrict__ G3, float* __restrict__ partU,
+                                                                float* __restrict__ part3) {
+  const int bx = xcd_block();
+  const int p0 = bx * ER_PT;
+  if (p0 >= M) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, g = lane >> 4;
+  const bool soft = md.wmax != nullptr;
+  const int npass = soft ? 2 : 1;
+  for (int cp = 0; cp < F1; cp += 128) {
+    const int cw = cp + wave * 32;
+    if (cw >= F1) continue;
+    float a_[2], s_[2], mu[2], is[2], a3_[2], s3_[2], mu3[2], is3[2];
+    float u1[2] = {0.f, 0.f}, u2[2] = {0.f, 0.f}, w1[2] = {0.f, 0.f}, w2[2] = {0.f, 0.f};
+    float t[2][4][2], mx[2][4][2], rs[2][4][2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+      const int c = cw + cb * 16 + col;
+      const bool ok = c < F1;
+      a_[cb] = ok ? sc[c] : 0.f; s_[cb] = ok ? sh[c] : 0.f; mu[cb] = ok ? mean[c] : 0.f; is[cb] = ok ? invstd[c] : 0.f;
+      a3_[cb] = ok ? md.sc3[c] : 0.f; s3_[cb] = ok ? md.sh3[c] : 0.f; mu3[cb] = ok ? mean3[c] : 0.f; is3[cb] = ok ? invstd3[c] : 0.f;
+#pragma unroll
+      for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int p = p0 + pb * 16 + 4 * g + v;
+          const bool on = soft && ok && p < M;
+          t[pb][v][cb] = 0.f;
+          mx[pb][v][cb] = on ? md.wmax[(size_t)p * F1 + c] : 0.f;
+          rs[pb][v][cb] = on ? md.wrs[(size_t)p * F1 + c] : 0.f;
+        }
+    }
+    for (int pass = 0; pass < npass; ++pass) {
+      const bool last = pass == npass - 1;
+      for (int r = 0; r < k; ++r) {
+        f32x4 acc[2][2];
+        acc[0][0] = acc[0][1] = acc[1][0] = acc[1][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (pass == 0) {
+          for (int ob = 0; ob < O; ob += 16) {
+            const int o = ob + 4 * g;
+            f32x4 a[2], b[2];
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb) {
+              const int p = p0 + pb * 16 + col;
+              a[pb] = ld4<VEC>(G + (size_t)min(p, M - 1) * ldg + o, p < M ? O - o : 0);
+            }
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+              const int c = cw + cb * 16 + col;
+              b[cb] = ld4<VEC>(Wt + ((size_t)r * F1 + min(c, F1 - 1)) * ldwt + o, c < F1 ? O - o : 0);
+            }
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+              for (int cb = 0; cb < 2; ++cb) acc[pb][cb] = mfma4(a[pb], b[cb], acc[pb][cb]);
+          }
+        }
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const int p = p0 + pb * 16 + 4 * g + v;
+            if (p >= M) continue;
+            const int n = neighbour(idx, p, k, r, M);
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+              const int c = cw + cb * 16 + col;
+              if (c < F1) {
+                const size_t e = ((size_t)p * k + r) * F1 + c;
+                const float dm = pass == 0 ? acc[pb][cb][v] : dU[e];
+                const float q = PQ[(size_t)p * ld + F1 + c], pv = PQ[(size_t)n * ld + c];
+                const float ah = pre_act(q, pv, a_[cb], s_[cb]);
+                const float z = md.z3[e];
+                const float a3 = fmaf(a3_[cb], z, s3_[cb]);
+                const float s = weight_s(lrelu_f(a3, slope), mx[pb][v][cb], rs[pb][v][cb], soft);
+                const float ds = dm * lrelu_f(ah, slope);
+                if (!last) {
+                  dU[e] = dm;
+                  t[pb][v][cb] = fmaf(ds, s, t[pb][v][cb]);
+                } else {
+                  const float du = lrelu_mask(ah, slope) * dm * s;
+                  const float g3 = lrelu_mask(a3, slope) * (soft ? s * (ds - t[pb][v][cb]) : ds);
+                  dU[e] = du;
+                  G3[e] = g3;
+                  u1[cb] += du;
+                  u2[cb] = fmaf(du, ((q + pv) - mu[cb]) * is[cb], u2[cb]);
+                  w1[cb] += g3;
+                  w2[cb] = fmaf(g3, (z - mu3[cb]) * is3[cb], w2[cb]);
+                }
+              }
+            }
+          }
+      }
+    }
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+      float a = u1[cb], b = u2[cb], c3 = w1[cb], d3 = w2[cb];
+      a += __shfl_xor(a, 16); b += __shfl_xor(b, 16); c3 += __shfl_xor(c3, 16); d3 += __shfl_xor(d3, 16);      // the four point groups, in a fixed order
+      a += __shfl_xor(a, 32); b += __shfl_xor(b, 32); c3 += __shfl_xor(c3, 32); d3 += __shfl_xor(d3, 32);
+      const int c = cw + cb * 16 + col;
+      if (g == 0 && c < F1) {
+        float* ru = partU + ((size_t)bx * F1 + c) * 2;
+        float* r3 = part3 + ((size_t)bx * F1 + c) * 2;
+        ru[0] = a; ru[1] = b;
+        r3[0] = c3; r3[1] = d3;
+      }
+    }
+  }
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool sizes_ok(int M, int k, int F1, int O) {
   return M > 0 && k >= 1 && k <= ER_KMAX && F1 > 0 && O > 0 && (long)M * k <= 0x7fffffffL && (long)k * F1 <= 0x7fffffffL;
@@ -453,8 +636,8 @@ extern "C" int spgan_edge_rank_gemm(const float* PQ, int ld, const int32_t* idx,
   const bool vec = F1 % 4 == 0 && ld % 4 == 0 && ldw % 4 == 0 && al16(PQ) && al16(W2i) && al16(scale1) && al16(shift1);
   const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
   hipStream_t st = (hipStream_t)s_;
-  if (vec) hipLaunchKernelGGL(edge_rank_gemm_kernel<true>, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials);
-  else hipLaunchKernelGGL(edge_rank_gemm_kernel<false>, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials);
+  if (vec) hipLaunchKernelGGL((edge_rank_gemm_kernel<true, false>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, WMod{});
+  else hipLaunchKernelGGL((edge_rank_gemm_kernel<false, false>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, WMod{});
   return spgan_launch_status();
 }
 
@@ -472,8 +655,8 @@ extern "C" int spgan_edge_rank_wgrad(const float* PQ, int ld, const int32_t* idx
   const bool vec = F1 % 4 == 0 && ld % 4 == 0 && al16(PQ) && al16(scale1) && al16(shift1);
   const dim3 gr(grid8((long)pl.tiles * pl.splits)), b(256);
   hipStream_t st = (hipStream_t)s_;
-  if (vec) hipLaunchKernelGGL(edge_rank_wgrad_kernel<true>, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl);
-  else hipLaunchKernelGGL(edge_rank_wgrad_kernel<false>, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl);
+  if (vec) hipLaunchKernelGGL((edge_rank_wgrad_kernel<true, false>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl, WMod{});
+  else hipLaunchKernelGGL((edge_rank_wgrad_kernel<false, false>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl, WMod{});
   int e = spgan_launch_status();
   if (e) return e;
   hipLaunchKernelGGL(edge_rank_wgrad_reduce_kernel, dim3(cdiv((long)O * k * F1 * 8, 256)), dim3(256), 0, st, ws, pl.splits, O, k * F1, dW2i, lddw);
@@ -513,5 +696,82 @@ extern "C" int spgan_edge_rank_scatter(const float* dA, const int32_t* rowptr, c
   else
     hipLaunchKernelGGL(edge_rank_scatter_kernel<1>, dim3(cdiv(items, 256)), dim3(256), 0, st, dA, rowptr, src, PQ, ld, idx, M, k, F1, scale1, mean1,
                        invstd1, sums, inv_e, dPQ, ldd);
+  return spgan_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------ the weighted layer (deform_edgeConv_feat)
+namespace {
+inline bool mod_ok(const float* z3, const float* sc3, const float* sh3, const float* wmax, const float* wrs) {
+  return z3 && sc3 && sh3 && ((wmax == nullptr) == (wrs == nullptr));
+}
+inline bool mod_al16(const WMod& m) { return al16(m.z3) && al16(m.sc3) && al16(m.sh3) && al16(m.wmax) && al16(m.wrs); }
+}  // namespace
+
+extern "C" int spgan_edge_weight_gather(const float* PQ, int ld, const int32_t* idx, int M, int k, int F, float* Z, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(PQ && idx && Z && sizes_ok(M, k, F, 1) && ld >= 2 * F && (long)M * k * F <= 0x7fffffffL * 256L);
+  hipLaunchKernelGGL(edge_weight_gather_kernel, dim3(cdiv((long)M * k * F, 256)), dim3(256), 0, (hipStream_t)s_, PQ, ld, idx, M, k, F, Z);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_edge_weight_norm(const float* z3, int M, int k, int F1, const float* scale3, const float* shift3, float slope, float* wmax,
+                                      float* wrs, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(z3 && scale3 && shift3 && wmax && wrs && sizes_ok(M, k, F1, 1) && (long)M * F1 <= 0x7fffffffL * 256L);
+  hipLaunchKernelGGL(edge_weight_norm_kernel, dim3(cdiv((long)M * F1, 256)), dim3(256), 0, (hipStream_t)s_, z3, M, k, F1, scale3, shift3, slope, wmax,
+                     wrs);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_edge_weight_gemm(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1,
+                                      float slope, const float* z3, const float* scale3, const float* shift3, const float* wmax, const float* wrs,
+                                      const float* W2i, int ldw, const float* b2, int O, float* Y, int ldy, float* partials, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(PQ && idx && scale1 && shift1 && W2i && Y && sizes_ok(M, k, F1, O) && ld >= 2 * F1 && ldw >= k * F1 && ldy >= O);
+  SPGAN_CHECK_ARG(mod_ok(z3, scale3, shift3, wmax, wrs));
+  const WMod md{z3, scale3, shift3, wmax, wrs};
+  const bool vec = F1 % 4 == 0 && ld % 4 == 0 && ldw % 4 == 0 && al16(PQ) && al16(W2i) && al16(scale1) && al16(shift1) && mod_al16(md);
+  const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
+  hipStream_t st = (hipStream_t)s_;
+  if (vec)
+    hipLaunchKernelGGL((edge_rank_gemm_kernel<true, true>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, md);
+  else
+    hipLaunchKernelGGL((edge_rank_gemm_kernel<false, true>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, md);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_edge_weight_wgrad(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1,
+                                       float slope, const float* z3, const float* scale3, const float* shift3, const float* wmax, const float* wrs,
+                                       const float* dY, int ldg, int O, float* dW2i, int lddw, float* ws, size_t ws_bytes, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(PQ && idx && scale1 && shift1 && dY && dW2i && ws && sizes_ok(M, k, F1, O) && ld >= 2 * F1 && ldg >= O && lddw >= k * F1);
+  SPGAN_CHECK_ARG(mod_ok(z3, scale3, shift3, wmax, wrs) && ws_bytes >= spgan_edge_rank_wgrad_ws_bytes(M, k, F1, O));
+  const WMod md{z3, scale3, shift3, wmax, wrs};
+  const RwPlan pl = er_wg_plan(M, k, F1, O);
+  const bool vec = F1 % 4 == 0 && ld % 4 == 0 && al16(PQ) && al16(scale1) && al16(shift1) && mod_al16(md);
+  const dim3 gr(grid8((long)pl.tiles * pl.splits)), b(256);
+  hipStream_t st = (hipStream_t)s_;
+  if (vec) hipLaunchKernelGGL((edge_rank_wgrad_kernel<true, true>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl, md);
+  else hipLaunchKernelGGL((edge_rank_wgrad_kernel<false, true>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl, md);
+  int e = spgan_launch_status();
+  if (e) return e;
+  hipLaunchKernelGGL(edge_rank_wgrad_reduce_kernel, dim3(cdiv((long)O * k * F1 * 8, 256)), dim3(256), 0, st, ws, pl.splits, O, k * F1, dW2i, lddw);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_edge_weight_dgrad(const float* dY, int ldg, const float* W2t, int ldwt, const float* PQ, int ld, const int32_t* idx, int M, int k,
+                                       int F1, int O, const float* scale1, const float* shift1, const float* mean1, const float* invstd1, float slope,
+                                       const float* z3, const float* scale3, const float* shift3, const float* mean3, const float* invstd3,
+                                       const float* wmax, const float* wrs, float* dU, float* G3, float* partials_u, float* partials_3,
+                                       spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(dY && W2t && PQ && idx && scale1 && shift1 && mean1 && invstd1 && sizes_ok(M, k, F1, O));
+  SPGAN_CHECK_ARG(mod_ok(z3, scale3, shift3, wmax, wrs) && mean3 && invstd3 && dU && G3 && dU != G3 && partials_u && partials_3);
+  SPGAN_CHECK_ARG(ldg >= O && ldwt >= O && ld >= 2 * F1);
+  const WMod md{z3, scale3, shift3, wmax, wrs};
+  const bool vec = O % 4 == 0 && ldg % 4 == 0 && ldwt % 4 == 0 && al16(dY) && al16(W2t);
+  const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
+  hipStream_t st = (hipStream_t)s_;
+  if (vec)
+    hipLaunchKernelGGL(edge_weight_dgrad_kernel<true>, gr, b, 0, st, dY, ldg, W2t, ldwt, PQ, ld, idx, M, k, F1, O, scale1, shift1, mean1, invstd1, slope, md,
+                       mean3, invstd3, dU, G3, partials_u, partials_3);
+  else
+    hipLaunchKernelGGL(edge_weight_dgrad_kernel<false>, gr, b, 0, st, dY, ldg, W2t, ldwt, PQ, ld, idx, M, k, F1, O, scale1, shift1, mean1, invstd1, slope, md,
+                       mean3, invstd3, dU, G3, partials_u, partials_3);
   return spgan_launch_status();
 }

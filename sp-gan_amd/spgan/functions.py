@@ -15,7 +15,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import edge_max, edge_rank, edge_window, nets, ops
+from . import edge_max, edge_rank, edge_weight, edge_window, nets, ops
 
 Tensor = torch.Tensor
 
@@ -876,6 +876,192 @@ class RankEdgeConvFn(Function):
             db2 = torch.zeros(Fout, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dy)[0]
         return (None, dx, dW1, db1, sums1[F1:].clone() if need[4] else None, sums1[:F1].clone() if need[5] else None,
                 dW2, db2, sums2[Fout:].clone() if need[8] else None, sums2[:Fout].clone() if need[9] else None)
+
+
+_WEIGHT_IMAGES: Dict[tuple, tuple] = {}
+
+
+def weight_images(Wh: Tensor, Wf1: Tensor, Wf2: Tensor, Wf3: Tensor, W2: Tensor):
+    """The operand images of deform_edgeConv_feat's five conv weights (inte_conv_hk.0 [Fin,2Fin,1,1], conv_fea.0 [16,2Fin,1,1], conv_fea.3
+    [64,16,1,1], conv_fea.6 [Fin,64,1,1], conv2.conv [Fout,Fin,1,k]):
+    (Wst_h [2Fin,Fin] and Wst_1 [32,Fin] = [Wd ; Wc - Wd] of the two per-point GEMMs, Wall_t [Fin, 2Fin+32] = their stack transposed,
+    Wm2 [64,16], Wm2^T, Wm3 [Fin,64], Wm3^T, W2i [Fout, k*Fin] tap-major, W2i^T).
+    Cached per weight set under the staleness rule of rank_images; inside a capture the images are rebuilt."""
+    def build():
+        def stack(W):
+            F_, C = W.shape[0], W.shape[1] // 2
+            Wm = W.reshape(F_, 2 * C)
+            return torch.cat([Wm[:, C:], Wm[:, :C] - Wm[:, C:]], dim=0)
+        Wst_h, Wst_1 = stack(Wh), stack(Wf1)
+        Wm2, Wm3 = Wf2.reshape(Wf2.shape[0], Wf2.shape[1]), Wf3.reshape(Wf3.shape[0], Wf3.shape[1])
+        W2i = W2[:, :, 0, :].permute(0, 2, 1).reshape(W2.shape[0], W2.shape[3] * W2.shape[1])
+        return (Wst_h, Wst_1, torch.cat([Wst_h, Wst_1], dim=0).t().contiguous(), Wm2.contiguous(), Wm2.t().contiguous(), Wm3.contiguous(),
+                Wm3.t().contiguous(), W2i, W2i.t().contiguous())
+    ws = tuple(w.detach() for w in (Wh, Wf1, Wf2, Wf3, W2))
+    Wh, Wf1, Wf2, Wf3, W2 = ws
+    if ops.capturing():
+        return build()
+    key = tuple(w.data_ptr() for w in ws) + tuple(tuple(w.shape) for w in ws)
+    stamp = tuple(ops.weights_epoch_of(w) for w in ws) + tuple(w._version for w in ws)
+    hit = _WEIGHT_IMAGES.get(key)
+    if hit is not None and hit[0] == stamp:
+        return hit[1]
+    if len(_WEIGHT_IMAGES) >= 64:
+        _WEIGHT_IMAGES.clear()
+    img = build()
+    _WEIGHT_IMAGES[key] = (stamp, img)
+    return img
+
+
+class WeightedRankEdgeConvFn(Function):
+    """out [B,Fout,N] = relu(bn_c(conv[1,k](h * s)))   (the reference's deform_edgeConv_feat, Generation/modules.py:1543-1599) with
+    h = lrelu(bn_h(conv1x1(e))), s = softmax over the k ranks of the shared three-layer MLP conv_fea(e) (or the MLP's output itself with
+    softmax=False) and e = cat[x_i, x_j - x_i], without e, h, s or h*s in memory, forward or backward.
+    Both first layers are per-point GEMMs (PQ_h [M,2Fin], PQ_1 [M,32], statistics from edge_max's gather pass); the MLP's narrow rows
+    z1 [M*k,16], z2 [M*k,64] and its pre-norm output z3 [M*k,Fin] (the one edge-sized tensor of the forward) are stored; the [1,k]
+    convolution forms h*s in LDS from gathered rows of PQ_h, z3 and the per-(point, channel) softmax normaliser (csrc/edge_rank.hip,
+    spgan.edge_weight).  The backward holds two further edge-sized buffers: du and g3 / dz3.
+    inputs: holder(B, N, k, training, softmax, idx | None, knn_mode, slope, bns = the five nn.BatchNorm2d modules (h, 1, 2, 3, c)),
+    x [B,Fin,N], then (conv weight, conv bias, bn weight, bn bias) of inte_conv_hk, conv_fea.0/1, conv_fea.3/4, conv_fea.6/7 and conv2.
+    Once differentiable, as RankEdgeConvFn.  Exact fp32 products: the layer does not follow ops.set_mfma_operands."""
+
+    @staticmethod
+    def forward(ctx, h, x, *params):
+        Wh, bh, gh, beh, Wf1, bf1, g1, be1, Wf2, bf2, g2, be2, Wf3, bf3, g3, be3, W2, b2, gc, bec = params
+        B, Fin, N = x.shape
+        k, M = h.k, B * N
+        E = M * k
+        x_pm = ops.cm_to_pm(x)
+        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
+        Wst_h, Wst_1, _, Wm2, _, Wm3, _, W2i, _ = weight_images(Wh, Wf1, Wf2, Wf3, W2)
+
+        def stats(bn, count, gamma, beta, records=None, moments=None):
+            """(scale, shift, invstd, mean) of one BatchNorm2d; train mode updates its buffers as nn.BatchNorm2d does"""
+            if not h.training:
+                return ops.bn_prepare(None, None, gamma, beta, count, False, bn.running_mean, bn.running_var, eps=float(bn.eps))
+            bn.num_batches_tracked += 1
+            if records is not None:
+                return edge_max.edge_max_bn(records[0], records[1], count, gamma, beta, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
+            return ops.bn_prepare(moments[0], moments[1], gamma, beta, count, True, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
+
+        # exact=True: fp32 operands whatever ops.set_mfma_operands selected
+        PQh = ops.gemm_nt(x_pm, Wst_h, torch.cat([torch.zeros_like(bh), bh]), exact=True)
+        PQ1 = ops.gemm_nt(x_pm, Wst_1, torch.cat([torch.zeros_like(bf1), bf1]), exact=True)
+        train = h.training
+        # the (sum, M2) records of Q_i + P_j over the M*k edges come from edge_max's gather pass; its max / min outputs are dropped
+        sth = stats(h.bns[0], E, gh, beh, records=edge_max.edge_max_gather(PQh, idx)[4:] if train else None)
+        st1 = stats(h.bns[1], E, g1, be1, records=edge_max.edge_max_gather(PQ1, idx)[4:] if train else None)
+        z1 = edge_weight.edge_weight_gather(PQ1, idx)
+        if train:
+            z2, m, v = ops.gemm_nt(z1, Wm2, bf2, pro=(st1[0], st1[1], h.slope), stats=True, exact=True)
+            st2 = stats(h.bns[2], E, g2, be2, moments=(m, v))
+            z3, m, v = ops.gemm_nt(z2, Wm3, bf3, pro=(st2[0], st2[1], h.slope), stats=True, exact=True)
+            st3 = stats(h.bns[3], E, g3, be3, moments=(m, v))
+        else:
+            st2 = stats(h.bns[2], E, g2, be2)
+            z2 = ops.gemm_nt(z1, Wm2, bf2, pro=(st1[0], st1[1], h.slope), exact=True)
+            st3 = stats(h.bns[3], E, g3, be3)
+            z3 = ops.gemm_nt(z2, Wm3, bf3, pro=(st2[0], st2[1], h.slope), exact=True)
+        norm = edge_weight.edge_weight_norm(z3, k, st3[0], st3[1], h.slope) if h.softmax else None
+        if train:
+            Y, part, rows = edge_weight.edge_weight_gemm(PQh, idx, sth[0], sth[1], z3, st3[0], st3[1], norm, W2i, b2, stats=True, slope=h.slope)
+            stc = stats(h.bns[4], M, gc, bec, records=(part, rows))
+            del part
+        else:
+            Y = edge_weight.edge_weight_gemm(PQh, idx, sth[0], sth[1], z3, st3[0], st3[1], norm, W2i, b2, slope=h.slope)
+            stc = stats(h.bns[4], M, gc, bec)
+        out_pm = ops.affine_act(Y, stc[0], stc[1], 0.0)
+        h.last_idx = idx
+        # the statistics are made here and handed to nobody else: they ride on ctx (see EdgeMaxConvFn)
+        ctx.h = h
+        ctx.st = tuple(tuple(st[i] for i in range(4)) for st in (sth, st1, st2, st3, stc))
+        ctx.norm = norm
+        ctx.save_for_backward(x, PQh, PQ1, z1, z2, z3, Y, idx, Wh, Wf1, Wf2, Wf3, W2, g2, g3, gc)
+        return ops.pm_to_cm(out_pm, B, N)
+
+    @staticmethod
+    def backward(ctx, dout):
+        if torch.is_grad_enabled():
+            raise RuntimeError("deform_edgeConv_feat is once differentiable: its backward was asked to build a graph (create_graph=True), but "
+                               "it has no double backward -- the layer cannot sit under a gradient penalty")
+        return WeightedRankEdgeConvFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        from . import pointnet_util
+        x, PQh, PQ1, z1, z2, z3, Y, idx, Wh, Wf1, Wf2, Wf3, W2, g2, g3, gc = ctx.saved_tensors
+        h = ctx.h
+        B, Fin, N = x.shape
+        k, M = h.k, B * N
+        E = M * k
+        Fout, F1, Fm = W2.shape[0], Wf1.shape[0], Wf2.shape[0]
+        (sch, shh, invh, muh), (sc1, sh1, inv1, mu1), (sc2, sh2, inv2, mu2), (sc3, sh3, inv3, mu3), (scc, shc, invc, muc) = ctx.st
+        need = ctx.needs_input_grad
+        train = h.training
+        dev = dout.device
+        _, _, Wall_t, _, Wm2t, _, Wm3t, _, W2t = weight_images(Wh, Wf1, Wf2, Wf3, W2)
+
+        def used(sums):                  # eval mode: the statistics are constants, the BatchNorm backward is the plain scale
+            return sums if train else torch.zeros_like(sums)
+
+        def dbias(rows):                 # a bias in front of a train-mode BatchNorm: exactly zero (the batch mean absorbs it)
+            return torch.zeros(rows.shape[1], dtype=torch.float32, device=dev) if train else ops.colsum(rows)[0]
+
+        # ReLU + BatchNorm of conv2
+        g = ops.cm_to_pm(dout.contiguous())
+        r, sumsc = pointnet_util._group_max_bwd(g, ops.affine_act(Y, scc, shc, 0.0), None, Y, muc, invc, 0.0, 1)
+        dy = ops.bn_bwd_apply(r, Y, muc, invc, gc, used(sumsc), M)
+        del g, r
+        # the product h*s, both LeakyReLUs and the softmax: du and g3 [M,k,Fin] are the two per-edge buffers of the backward
+        du, sumsh, gz3, sums3 = edge_weight.edge_weight_dgrad(dy, W2t, PQh, idx, sch, shh, muh, invh, z3, sc3, sh3, mu3, inv3, ctx.norm, h.slope)
+        rowptr, src = ops.csr_build(idx, B, N)
+        if train:
+            dPQh = edge_rank.edge_rank_scatter(du, rowptr, src, sch, PQh, idx, muh, invh, sumsh)
+        else:
+            dPQh = edge_rank.edge_rank_scatter(du, rowptr, src, sch)
+        del du
+        # the weight MLP, last layer first
+        dz3 = ops.bn_bwd_apply(gz3, z3, mu3, inv3, g3, used(sums3), E)
+        del gz3
+        dWf3 = ops.gemm_tn(dz3, z2, pro=(sc2, sh2, h.slope), exact=True).view(Fin, Fm, 1, 1) if need[14] else None
+        dbf3 = dbias(dz3) if need[15] else None
+        gz2, t1, t2 = ops.gemm_nt_bnbwd(dz3, Wm3t, z2, sc2, sh2, mu2, inv2, h.slope, exact=True)
+        del dz3
+        sums2 = torch.cat([t1, t2])
+        dz2 = ops.bn_bwd_apply(gz2, z2, mu2, inv2, g2, used(sums2), E)
+        del gz2
+        dWf2 = ops.gemm_tn(dz2, z1, pro=(sc1, sh1, h.slope), exact=True).view(Fm, F1, 1, 1) if need[10] else None
+        dbf2 = dbias(dz2) if need[11] else None
+        gz1, t1, t2 = ops.gemm_nt_bnbwd(dz2, Wm2t, z1, sc1, sh1, mu1, inv1, h.slope, exact=True)
+        del dz2
+        sums1 = torch.cat([t1, t2])
+        if train:
+            dPQ1 = edge_rank.edge_rank_scatter(gz1.view(M, k, F1), rowptr, src, sc1, PQ1, idx, mu1, inv1, sums1)
+        else:
+            dPQ1 = edge_rank.edge_rank_scatter(gz1.view(M, k, F1), rowptr, src, sc1)
+        del gz1
+        dW2 = None
+        if need[18]:                                                     # after du and g3 have died: its split workspace is not held beside them
+            dW2 = edge_weight.edge_weight_wgrad(PQh, idx, sch, shh, z3, sc3, sh3, ctx.norm, dy, h.slope)
+            dW2 = dW2.view(Fout, k, Fin).permute(0, 2, 1).unsqueeze(2).contiguous()
+        dPQ = torch.cat([dPQh, dPQ1], dim=1)                             # [M, 2Fin + 32]: both branches feed one product pair
+        dWh = dWf1 = None
+        if need[2] or need[6]:
+            dWst = ops.gemm_tn(dPQ, ops.cm_to_pm(x), exact=True)                     # rows of dW'_P, then of dW'_Q, per branch
+
+            def conv_grad(d, F_):                                        # dWc = dW'_Q, dWd = dW'_P - dW'_Q
+                return torch.cat([d[F_:], d[:F_] - d[F_:]], dim=1).view(F_, 2 * Fin, 1, 1)
+            dWh, dWf1 = conv_grad(dWst[:2 * Fin], Fin), conv_grad(dWst[2 * Fin:], F1)
+        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wall_t, exact=True), B, N) if need[1] else None
+        dbh = dbias(dPQh[:, Fin:]) if need[3] else None
+        dbf1 = dbias(dPQ1[:, F1:]) if need[7] else None
+        db2 = dbias(dy) if need[19] else None
+
+        def gb(sums, F_, i):             # (dgamma, dbeta) = (sum g*xhat, sum g)
+            return (sums[F_:].clone() if need[i] else None, sums[:F_].clone() if need[i + 1] else None)
+        return (None, dx, dWh, dbh) + gb(sumsh, Fin, 4) + (dWf1, dbf1) + gb(sums1, F1, 8) + (dWf2, dbf2) + gb(sums2, Fm, 12) + \
+            (dWf3, dbf3) + gb(sums3, Fin, 16) + (dW2, db2) + gb(sumsc, Fout, 20)
 
 
 class EdgeFeaturesFn(Function):

@@ -820,3 +820,74 @@ class deform_edgeConv_first(_RankEdgeConv):
     def forward(self, x, idx: Optional[torch.Tensor] = None):
         out = self._run(x, idx)
         return out.view(out.shape[0], out.shape[1], out.shape[2], 1, 1)
+
+
+class deform_edgeConv_feat(nn.Module):
+    """Generation/modules.py:1543-1599: [B,Fin,N] -> [B,Fout,N], conv2dbr(Fin -> Fout, [1,k]) over inte_conv_hk(e) * w with e =
+    get_edge_features(x), inte_conv_hk = Conv2d(2Fin -> Fin, 1x1) + BatchNorm2d + LeakyReLU and w = conv_fea(e), a shared MLP
+    2Fin -> 16 -> 64 -> Fin (each Conv2d 1x1 + BatchNorm2d + LeakyReLU), normalised by a softmax over the k neighbours (softmax=True).
+    Evaluated by Fn.WeightedRankEdgeConvFn (csrc/edge_rank.hip): e, the activated tensor, the weight and their product never exist in
+    memory; the forward keeps one [B*N,k,Fin] tensor, the backward two more.  The sub-modules are parameter containers in the reference's
+    order and names (state_dicts load strictly both ways).  idx (an extension, as edgeConv's): the graph to use instead of the kNN graph
+    of x, int64 [B, N*k] local indices (range-checked outside a capture) or int32 [B*N,k] global rows (trusted).  1 <= k <= 32.  Once
+    differentiable.  last_idx: the graph of the latest forward."""
+
+    def __init__(self, Fin, Fout, k, softmax=True):
+        super().__init__()
+        if not 1 <= k <= 32:
+            raise ValueError("deform_edgeConv_feat: k must lie in 1..32, got k=%d (Fin=%d, Fout=%d)" % (k, Fin, Fout))
+        if Fin < 1 or Fout < 1:
+            raise ValueError("deform_edgeConv_feat: Fin and Fout must be positive, got Fin=%d, Fout=%d" % (Fin, Fout))
+        self.k = k
+        self.Fin = Fin
+        self.Fout = Fout
+        self.softmax = softmax
+        self.conv2 = conv2dbr(Fin, Fout, [1, k], [1, 1])
+        self.conv_fea = nn.Sequential(
+            nn.Conv2d(2 * Fin, 16, 1),
+            nn.BatchNorm2d(16),
+            nn.LeakyReLU(inplace=True),
+            nn.Conv2d(16, 64, 1),
+            nn.BatchNorm2d(64),
+            nn.LeakyReLU(inplace=True),
+            nn.Conv2d(64, Fin, 1),
+            nn.BatchNorm2d(Fin),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.inte_conv_hk = nn.Sequential(
+            nn.Conv2d(2 * Fin, Fin, [1, 1], [1, 1]),
+            nn.BatchNorm2d(Fin),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.last_idx: Optional[torch.Tensor] = None
+
+    def forward(self, x, idx: Optional[torch.Tensor] = None):
+        name = "deform_edgeConv_feat"
+        _require_gpu(x, name)
+        B, Fin, N = x.shape
+        if Fin != self.Fin:
+            raise ValueError("%s(%d, %d, %d) got an input with %d channels" % (name, self.Fin, self.Fout, self.k, Fin))
+        layers = [(self.inte_conv_hk[0], self.inte_conv_hk[1])] + [(self.conv_fea[i], self.conv_fea[i + 1]) for i in (0, 3, 6)] + \
+            [(self.conv2.conv, self.conv2.bn)]
+        for _, bn in layers:
+            if bn.momentum is None or not bn.track_running_stats:
+                raise NotImplementedError("%s: BatchNorm2d with momentum=None or track_running_stats=False is not supported" % name)
+        slopes = {float(a.negative_slope) for a in (self.inte_conv_hk[2], self.conv_fea[2], self.conv_fea[5], self.conv_fea[8])}
+        if len(slopes) != 1:
+            raise NotImplementedError("%s: the four LeakyReLUs must share one slope, got %s" % (name, sorted(slopes)))
+        if idx is not None:
+            _require_gpu(idx, name + " idx")
+            if idx.dtype == torch.int64:
+                if idx.numel() != B * N * self.k:
+                    raise ValueError("%s: idx must hold B*N*k = %d indices, got %s" % (name, B * N * self.k, tuple(idx.shape)))
+                if not ops.capturing() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+                    raise IndexError("%s: a neighbour index lies outside [0, %d)" % (name, N))
+                idx = ops.idx_from_local64(idx.reshape(B, N * self.k), B, N, self.k)
+            elif idx.dtype != torch.int32 or tuple(idx.shape) != (B * N, self.k):
+                raise ValueError("%s: idx must be int64 [B, N*k] (local) or int32 [B*N, k] (global rows)" % name)
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, softmax=bool(self.softmax), idx=idx, knn_mode=1 if Fin <= 4 else 0,
+                    slope=slopes.pop(), bns=tuple(bn for _, bn in layers), last_idx=None)
+        params = [t for conv, bn in layers for t in (conv.weight, conv.bias, bn.weight, bn.bias)]
+        out = Fn.WeightedRankEdgeConvFn.apply(h, x.contiguous(), *params)
+        self.last_idx = h.last_idx
+        return out

@@ -620,14 +620,16 @@ def bn_dbl_phaseb(coeffs, gamma: Tensor, invstd: Tensor, s0: Optional[Tensor], s
 
 
 def gemm_nt_bnbwd(A, W: Tensor, y_ref: Tensor, scale: Tensor, shift: Tensor, mean: Tensor, invstd: Tensor, slope: float,
-                  edge=None, pro=None, bias: Optional[Tensor] = None, rowadd: Optional[Tensor] = None, coef_bn=None, phaseb=None, gout=None):
+                  edge=None, pro=None, bias: Optional[Tensor] = None, rowadd: Optional[Tensor] = None, coef_bn=None, phaseb=None, gout=None,
+                  exact: bool = False):
     """g = (pro(A) @ W^T + bias + rowadd) * lrelu'(z), z = y*scale+shift; returns (g, sum_c g, sum_c g*xhat), xhat = (y-mean)*invstd.
     With edge=(idx, ebias) y is the per-edge difference y[e] = P[idx[e]] - P[i] + ebias of the point tensor P=y_ref.
     A may be a SparseAffine or an Affine2 operand; pro=(scale[K], shift[K], slope) as in gemm_nt; rowadd is a dense [M,N] addend.
     coef_bn = (gamma | None, count): also return the BatchNorm-backward coefficients coef [3,N] of bn_bwd_lazy(g, y_ref, mean, invstd,
     gamma, [sum g | sum g*xhat], count) as a fourth result -- emitted by the launch that finishes the column sums (not with edge).
     phaseb / gout: as gemm_dual's (the double backward's phase B: the finalize launch also runs bn_dbl_phaseb on the sums it merges, the
-    stored tensor is gout[0] + gout[1]*g) -> (g, s0, s1, sums, dgamma [, coef]); M > 64, no per-edge operand, not together with coef_bn."""
+    stored tensor is gout[0] + gout[1]*g) -> (g, s0, s1, sums, dgamma [, coef]); M > 64, no per-edge operand, not together with coef_bn.
+    exact=True keeps fp32 operands whatever set_mfma_operands selected, as gemm_nt's."""
     if (phaseb is not None or gout is not None) and (edge is not None or coef_bn is not None):
         raise ValueError("gemm_nt_bnbwd: phaseb / gout take neither a per-edge operand nor coef_bn")
     sa = A if isinstance(A, SparseAffine) else None
@@ -651,7 +653,7 @@ def gemm_nt_bnbwd(A, W: Tensor, y_ref: Tensor, scale: Tensor, shift: Tensor, mea
     g = torch.empty((M_, N), dtype=torch.float32, device=A.device)
     tiles = (M_ + ROW_TILE - 1) // ROW_TILE
     part = torch.empty((tiles, N, 2), dtype=torch.float32, device=A.device)
-    a = GemmNTArgs(); a.mfma_f16 = _MFMA_F16[0]; a.tile_hint = _NT_TILE_HINT[0]
+    a = GemmNTArgs(); a.mfma_f16 = 0 if exact else _MFMA_F16[0]; a.tile_hint = _NT_TILE_HINT[0]
     a.A = _p(A); a.lda = _ld(A); a.W = _p(W); a.ldw = _ld(W); a.Y = _p(g); a.ldy = N
     a.M, a.N, a.K = M_, N, K
     a.a_mode = A_PLAIN
