@@ -223,7 +223,14 @@ __global__ __launch_bounds__(256) void edge_attend_bwd_kernel(
           const float zy = fmaf(yp, ax, cx);
           const float yv = lrelu_f(zy, slope);
           const float d = dTi[(size_t)r * F + f];
-          const float ds = wgt * (d * yv - dot);            // softmax backward
+          float dw;
+          {
+            // the ROUNDED product, as it went into `dot`: contracted into the subtraction below it would be the exact one, and at
+            // k = 1, where dot == dw, the difference would be the product's rounding residue instead of 0
+#pragma clang fp contract(off)
+            dw = d * yv;
+          }
+          const float ds = wgt * (dw - dot);                // softmax backward
           const float o2 = ds * lrelu_mask(z2, slope);
           const float oy = d * wgt * lrelu_mask(zy, slope);
           g2[((size_t)i * k + r) * F + f] = o2;
