@@ -621,6 +621,43 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 inline bool sizes_ok(int M, int k, int F1, int O) {
   return M > 0 && k >= 1 && k <= ER_KMAX && F1 > 0 && O > 0 && (long)M * k <= 0x7fffffffL && (long)k * F1 <= 0x7fffffffL;
 }
+inline bool mod_ok(const float* z3, const float* sc3, const float* sh3, const float* wmax, const float* wrs) {
+  return z3 && sc3 && sh3 && ((wmax == nullptr) == (wrs == nullptr));
+}
+inline bool mod_al16(const WMod& m) { return al16(m.z3) && al16(m.sc3) && al16(m.sh3) && al16(m.wmax) && al16(m.wrs); }
+
+// The [1,k] product and its weight gradient, plain (md == nullptr: spgan_edge_rank_*) or with the per-edge weight (spgan_edge_weight_*).
+int launch_gemm(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1, float slope,
+                const float* W2i, int ldw, const float* b2, int O, float* Y, int ldy, float* partials, const WMod* md, hipStream_t st) {
+  const bool vec = F1 % 4 == 0 && ld % 4 == 0 && ldw % 4 == 0 && al16(PQ) && al16(W2i) && al16(scale1) && al16(shift1) && (!md || mod_al16(*md));
+  const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
+  auto go = [&](auto kernel, const WMod& m) {
+    hipLaunchKernelGGL(kernel, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, m);
+  };
+  if (md && vec) go(edge_rank_gemm_kernel<true, true>, *md);
+  else if (md) go(edge_rank_gemm_kernel<false, true>, *md);
+  else if (vec) go(edge_rank_gemm_kernel<true, false>, WMod{});
+  else go(edge_rank_gemm_kernel<false, false>, WMod{});
+  return spgan_launch_status();
+}
+
+int launch_wgrad(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1, float slope,
+                 const float* dY, int ldg, int O, float* dW2i, int lddw, float* ws, const WMod* md, hipStream_t st) {
+  const RwPlan pl = er_wg_plan(M, k, F1, O);
+  const bool vec = F1 % 4 == 0 && ld % 4 == 0 && al16(PQ) && al16(scale1) && al16(shift1) && (!md || mod_al16(*md));
+  const dim3 gr(grid8((long)pl.tiles * pl.splits)), b(256);
+  auto go = [&](auto kernel, const WMod& m) {
+    hipLaunchKernelGGL(kernel, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl, m);
+  };
+  if (md && vec) go(edge_rank_wgrad_kernel<true, true>, *md);
+  else if (md) go(edge_rank_wgrad_kernel<false, true>, *md);
+  else if (vec) go(edge_rank_wgrad_kernel<true, false>, WMod{});
+  else go(edge_rank_wgrad_kernel<false, false>, WMod{});
+  int e = spgan_launch_status();
+  if (e) return e;
+  hipLaunchKernelGGL(edge_rank_wgrad_reduce_kernel, dim3(cdiv((long)O * k * F1 * 8, 256)), dim3(256), 0, st, ws, pl.splits, O, k * F1, dW2i, lddw);
+  return spgan_launch_status();
+}
 
 }  // namespace
 
@@ -633,12 +670,7 @@ extern "C" int spgan_edge_rank_gemm(const float* PQ, int ld, const int32_t* idx,
                                     float slope, const float* W2i, int ldw, const float* b2, int O, float* Y, int ldy, float* partials,
                                     spgan_stream_t s_) {
   SPGAN_CHECK_ARG(PQ && idx && scale1 && shift1 && W2i && Y && sizes_ok(M, k, F1, O) && ld >= 2 * F1 && ldw >= k * F1 && ldy >= O);
-  const bool vec = F1 % 4 == 0 && ld % 4 == 0 && ldw % 4 == 0 && al16(PQ) && al16(W2i) && al16(scale1) && al16(shift1);
-  const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
-  hipStream_t st = (hipStream_t)s_;
-  if (vec) hipLaunchKernelGGL((edge_rank_gemm_kernel<true, false>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, WMod{});
-  else hipLaunchKernelGGL((edge_rank_gemm_kernel<false, false>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, WMod{});
-  return spgan_launch_status();
+  return launch_gemm(PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, nullptr, (hipStream_t)s_);
 }
 
 extern "C" size_t spgan_edge_rank_wgrad_ws_bytes(int M, int k, int F1, int O) {
@@ -651,16 +683,7 @@ extern "C" int spgan_edge_rank_wgrad(const float* PQ, int ld, const int32_t* idx
                                      spgan_stream_t s_) {
   SPGAN_CHECK_ARG(PQ && idx && scale1 && shift1 && dY && dW2i && ws && sizes_ok(M, k, F1, O) && ld >= 2 * F1 && ldg >= O && lddw >= k * F1);
   SPGAN_CHECK_ARG(ws_bytes >= spgan_edge_rank_wgrad_ws_bytes(M, k, F1, O));
-  const RwPlan pl = er_wg_plan(M, k, F1, O);
-  const bool vec = F1 % 4 == 0 && ld % 4 == 0 && al16(PQ) && al16(scale1) && al16(shift1);
-  const dim3 gr(grid8((long)pl.tiles * pl.splits)), b(256);
-  hipStream_t st = (hipStream_t)s_;
-  if (vec) hipLaunchKernelGGL((edge_rank_wgrad_kernel<true, false>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl, WMod{});
-  else hipLaunchKernelGGL((edge_rank_wgrad_kernel<false, false>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl, WMod{});
-  int e = spgan_launch_status();
-  if (e) return e;
-  hipLaunchKernelGGL(edge_rank_wgrad_reduce_kernel, dim3(cdiv((long)O * k * F1 * 8, 256)), dim3(256), 0, st, ws, pl.splits, O, k * F1, dW2i, lddw);
-  return spgan_launch_status();
+  return launch_wgrad(PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, dW2i, lddw, ws, nullptr, (hipStream_t)s_);
 }
 
 extern "C" int spgan_edge_rank_dgrad(const float* dY, int ldg, const float* W2t, int ldwt, const float* PQ, int ld, const int32_t* idx, int M, int k,
@@ -700,13 +723,6 @@ extern "C" int spgan_edge_rank_scatter(const float* dA, const int32_t* rowptr, c
 }
 
 // ------------------------------------------------------------------------------------------ the weighted layer (deform_edgeConv_feat)
-namespace {
-inline bool mod_ok(const float* z3, const float* sc3, const float* sh3, const float* wmax, const float* wrs) {
-  return z3 && sc3 && sh3 && ((wmax == nullptr) == (wrs == nullptr));
-}
-inline bool mod_al16(const WMod& m) { return al16(m.z3) && al16(m.sc3) && al16(m.sh3) && al16(m.wmax) && al16(m.wrs); }
-}  // namespace
-
 extern "C" int spgan_edge_weight_gather(const float* PQ, int ld, const int32_t* idx, int M, int k, int F, float* Z, spgan_stream_t s_) {
   SPGAN_CHECK_ARG(PQ && idx && Z && sizes_ok(M, k, F, 1) && ld >= 2 * F && (long)M * k * F <= 0x7fffffffL * 256L);
   hipLaunchKernelGGL(edge_weight_gather_kernel, dim3(cdiv((long)M * k * F, 256)), dim3(256), 0, (hipStream_t)s_, PQ, ld, idx, M, k, F, Z);
@@ -727,14 +743,7 @@ extern "C" int spgan_edge_weight_gemm(const float* PQ, int ld, const int32_t* id
   SPGAN_CHECK_ARG(PQ && idx && scale1 && shift1 && W2i && Y && sizes_ok(M, k, F1, O) && ld >= 2 * F1 && ldw >= k * F1 && ldy >= O);
   SPGAN_CHECK_ARG(mod_ok(z3, scale3, shift3, wmax, wrs));
   const WMod md{z3, scale3, shift3, wmax, wrs};
-  const bool vec = F1 % 4 == 0 && ld % 4 == 0 && ldw % 4 == 0 && al16(PQ) && al16(W2i) && al16(scale1) && al16(shift1) && mod_al16(md);
-  const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
-  hipStream_t st = (hipStream_t)s_;
-  if (vec)
-    hipLaunchKernelGGL((edge_rank_gemm_kernel<true, true>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, md);
-  else
-    hipLaunchKernelGGL((edge_rank_gemm_kernel<false, true>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, md);
-  return spgan_launch_status();
+  return launch_gemm(PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, &md, (hipStream_t)s_);
 }
 
 extern "C" int spgan_edge_weight_wgrad(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1,
@@ -743,16 +752,7 @@ extern "C" int spgan_edge_weight_wgrad(const float* PQ, int ld, const int32_t* i
   SPGAN_CHECK_ARG(PQ && idx && scale1 && shift1 && dY && dW2i && ws && sizes_ok(M, k, F1, O) && ld >= 2 * F1 && ldg >= O && lddw >= k * F1);
   SPGAN_CHECK_ARG(mod_ok(z3, scale3, shift3, wmax, wrs) && ws_bytes >= spgan_edge_rank_wgrad_ws_bytes(M, k, F1, O));
   const WMod md{z3, scale3, shift3, wmax, wrs};
-  const RwPlan pl = er_wg_plan(M, k, F1, O);
-  const bool vec = F1 % 4 == 0 && ld % 4 == 0 && al16(PQ) && al16(scale1) && al16(shift1) && mod_al16(md);
-  const dim3 gr(grid8((long)pl.tiles * pl.splits)), b(256);
-  hipStream_t st = (hipStream_t)s_;
-  if (vec) hipLaunchKernelGGL((edge_rank_wgrad_kernel<true, true>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl, md);
-  else hipLaunchKernelGGL((edge_rank_wgrad_kernel<false, true>), gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl, md);
-  int e = spgan_launch_status();
-  if (e) return e;
-  hipLaunchKernelGGL(edge_rank_wgrad_reduce_kernel, dim3(cdiv((long)O * k * F1 * 8, 256)), dim3(256), 0, st, ws, pl.splits, O, k * F1, dW2i, lddw);
-  return spgan_launch_status();
+  return launch_wgrad(PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, dW2i, lddw, ws, &md, (hipStream_t)s_);
 }
 
 extern "C" int spgan_edge_weight_dgrad(const float* dY, int ldg, const float* W2t, int ldwt, const float* PQ, int ld, const int32_t* idx, int M, int k,

@@ -6,7 +6,7 @@
 Importing the package does not touch the GPU; the shared library is loaded on first use and its
 absence is a hard error (there is no CPU fallback).
 """
-from . import dataset, edge_max, edge_rank, edge_weight, edge_window, fixture_rng, metrics, ops, pointconv_util, pointnet_util, sampling  # noqa: F401
+from . import dataset, edge_conv, edge_max, edge_rank, edge_weight, edge_window, fixture_rng, metrics, ops, pointconv_util, pointnet_util, sampling  # noqa: F401
 from .capture import CapturedBody                                          # noqa: F401
 from .losses import GradientPenalty, dis_loss, gen_loss                    # noqa: F401
 from .modules import (AdaptivePointNorm, Discriminator, EdgeBlock, Generator, conv2dbr, deform_edgeConv_feat,            # noqa: F401

@@ -1,0 +1,485 @@
+"""The gather-side edge convolutions: the autograd Functions behind `spgan.edgeConv`, `upsample_edgeConv`, `deform_edgeConv_simple` /
+`_first` and `deform_edgeConv_feat`, over the launchers of spgan.edge_max / edge_window / edge_rank / edge_weight.
+
+The family's conventions, stated once:
+* A 1x1 convolution over the edge features cat[x_i, x_j - x_i] is one per-point GEMM, PQ [M,2F] = [P | Q] = x.[Wd ; Wc - Wd]^T + [0 ; b]
+  (`stacked` / `unstacked_grad`); the value on edge (i, j) is Q_i + P_j and exists only inside the kernels.
+* idx is int32 [M,k] with global rows (M = B*N), made by ops.knn or handed in through the holder (modules.check_edge_input).
+* Each Function takes holder(B, N, k, training, idx | None, knn_mode, the nn.BatchNorm2d modules, ...), x [B,Fin,N], then (conv weight,
+  conv bias, bn weight, bn bias) per layer.  The holder's last_idx receives the graph of the forward.
+* The statistics (scale, shift, invstd, mean) of every BatchNorm are made in forward (`bn_stats`) and handed to nobody else: nothing can
+  write them between forward and backward, so they ride on ctx instead of through save_for_backward's version check.  The running
+  statistics that ARE updated in place are not read by the backward.
+* Once differentiable: a selection or a mask is piecewise constant and the backward is a closed form over saved statistics, so a second
+  derivative is refused where it is asked for (`refuse_double_backward`): no GradientPenalty on top of these layers.
+* The rank layers (RankEdgeConvFn's [1,k] product, all of WeightedRankEdgeConvFn) compute exact fp32 products: they do not follow
+  ops.set_mfma_operands.
+* Weight-derived operand images are cached per weight set (`cached_images`)."""
+from __future__ import annotations
+
+from typing import Callable, Dict, Sequence
+
+import torch
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+
+from . import edge_max, edge_rank, edge_weight, edge_window, ops
+
+Tensor = torch.Tensor
+
+
+# ----------------------------------------------------------------------------- operand images
+# one dictionary per builder: a layer that reaches the cap does not evict another layer's images
+_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}}
+
+
+def cached_images(cache: Dict[tuple, tuple], weights: Sequence[Tensor], extra: tuple, build: Callable):
+    """build(*detached weights), cached in `cache` until a weight changes: the key is the weights' (data_ptr, shape) and `extra`; an entry is stale
+    once a weight's (ops.weights_epoch_of, torch version counter) stamp moves -- an in-place write, or an optimiser step of
+    spgan.optim.Adam, which rewrites parameters invisibly to torch and bumps the epoch of their storage (the staleness rule of nets._t).
+    Inside a capture the cache is neither read nor written: the images are rebuilt there, so that their kernels are part of the graph
+    and every replay sees the weights of that moment.  The dictionary is cleared when it holds 64 entries."""
+    ws = [w.detach() for w in weights]
+    if ops.capturing():
+        return build(*ws)
+    key = (extra,) + tuple([(w.data_ptr(), w.shape) for w in ws])
+    stamp = [(ops.weights_epoch_of(w), w._version) for w in ws]
+    hit = cache.get(key)
+    if hit is not None and hit[0] == stamp:
+        return hit[1]
+    if len(cache) >= 64:
+        cache.clear()
+    img = build(*ws)
+    cache[key] = (stamp, img)
+    return img
+
+
+def stacked(W: Tensor) -> Tensor:
+    """conv weight [F,2C,1,1] over cat[x_i, x_j - x_i] -> [Wd ; Wc - Wd] [2F,C]: rows of P, then rows of Q"""
+    F_, C = W.shape[0], W.shape[1] // 2
+    Wm = W.reshape(F_, 2 * C)
+    Wd = Wm[:, C:]
+    return torch.cat([Wd, Wm[:, :C] - Wd], dim=0)
+
+
+def unstacked_grad(dWst: Tensor) -> Tensor:
+    """[2F,C], rows of dW'_P, then of dW'_Q -> the conv weight's gradient [F,2C,1,1]: dWc = dW'_Q, dWd = dW'_P - dW'_Q"""
+    F_ = dWst.shape[0] // 2
+    return torch.cat([dWst[F_:], dWst[:F_] - dWst[F_:]], dim=1).view(F_, 2 * dWst.shape[1], 1, 1)
+
+
+def pq_bias(b: Tensor) -> Tensor:
+    return torch.cat([torch.zeros_like(b), b])                          # the conv bias belongs to the central half: Q
+
+
+def upsample_images(W1: Tensor, V: Tensor, C: int, k: int):
+    """The operand images of upsample_edgeConv's two conv weights (W1 [4C,2C,1,w], V [F2,2C,1,2k]):
+    (Wc1 [4C,C], Wd1 [4C,w*C], Wd1^T, Vc [F2,C], Vd [F2,k*C], Vd^T, V2p [F2,T*4C], V2p^T, Wc1^T, Vc^T).
+    Wc = the central halves summed over the taps; Wd = the difference halves, tap-major; V2p = conv2's last k taps with the columns
+    permuted from the reference's per-point (2C, k) reading, c'*k + j = o*T + t, to this layer's row order t*4C + o.
+    Cached per weight pair (cached_images)."""
+    def build(W1, V):
+        w = W1.shape[3]
+        T = k - w + 1
+        F2 = V.shape[0]
+        Wc1 = W1[:, :C, 0, :].sum(dim=2)
+        Wd1 = W1[:, C:, 0, :].permute(0, 2, 1).reshape(4 * C, w * C)
+        Vc = V[:, :C, 0, :k].sum(dim=2)
+        Vd = V[:, C:, 0, :k].permute(0, 2, 1).reshape(F2, k * C)
+        V2p = V[:, :, 0, k:].reshape(F2, 4 * C, T).permute(0, 2, 1).reshape(F2, T * 4 * C)
+        return (Wc1, Wd1, Wd1.t().contiguous(), Vc, Vd, Vd.t().contiguous(), V2p, V2p.t().contiguous(), Wc1.t().contiguous(),
+                Vc.t().contiguous())
+    return cached_images(_IMAGES["upsample"], (W1, V), (C, k), build)
+
+
+def rank_images(W1: Tensor, W2: Tensor):
+    """The operand images of the full-rank edge convolution's two conv weights (W1 [F1,2Fin,1,1], W2 [Fout,F1,1,k]):
+    (Wst [2F1,Fin] = [Wd ; Wc - Wd] (rows of P, then of Q), Wst^T, W2i [Fout, k*F1] tap-major (column r*F1 + c), W2i^T).
+    Cached per weight pair (cached_images)."""
+    def build(W1, W2):
+        Wst = stacked(W1)
+        W2i = W2[:, :, 0, :].permute(0, 2, 1).reshape(W2.shape[0], W2.shape[3] * W2.shape[1])
+        return Wst, Wst.t().contiguous(), W2i, W2i.t().contiguous()
+    return cached_images(_IMAGES["rank"], (W1, W2), (), build)
+
+
+def weight_images(Wh: Tensor, Wf1: Tensor, Wf2: Tensor, Wf3: Tensor, W2: Tensor):
+    """The operand images of deform_edgeConv_feat's five conv weights (inte_conv_hk.0 [Fin,2Fin,1,1], conv_fea.0 [16,2Fin,1,1], conv_fea.3
+    [64,16,1,1], conv_fea.6 [Fin,64,1,1], conv2.conv [Fout,Fin,1,k]):
+    (Wst_h [2Fin,Fin] and Wst_1 [32,Fin] = [Wd ; Wc - Wd] of the two per-point GEMMs, Wall_t [Fin, 2Fin+32] = their stack transposed,
+    Wm2 [64,16], Wm2^T, Wm3 [Fin,64], Wm3^T, W2i [Fout, k*Fin] tap-major, W2i^T).
+    Cached per weight set (cached_images)."""
+    def build(Wh, Wf1, Wf2, Wf3, W2):
+        Wst_h, Wst_1 = stacked(Wh), stacked(Wf1)
+        Wm2, Wm3 = Wf2.reshape(Wf2.shape[0], Wf2.shape[1]), Wf3.reshape(Wf3.shape[0], Wf3.shape[1])
+        W2i = W2[:, :, 0, :].permute(0, 2, 1).reshape(W2.shape[0], W2.shape[3] * W2.shape[1])
+        return (Wst_h, Wst_1, torch.cat([Wst_h, Wst_1], dim=0).t().contiguous(), Wm2.contiguous(), Wm2.t().contiguous(), Wm3.contiguous(),
+                Wm3.t().contiguous(), W2i, W2i.t().contiguous())
+    return cached_images(_IMAGES["weight"], (Wh, Wf1, Wf2, Wf3, W2), (), build)
+
+
+# ----------------------------------------------------------------------------- what the Functions share
+def refuse_double_backward(layer: str) -> None:
+    """First line of every backward.  @once_differentiable alone fails late and only when the cotangent carries a graph; with
+    create_graph=True and a plain cotangent (autograd.grad(out.sum(), x, create_graph=True): the gradient-penalty pattern) it would hand
+    back a gradient without a graph and the penalty's second derivative would silently be missing.  Refuse where the request is made."""
+    if torch.is_grad_enabled():
+        raise RuntimeError("%s is once differentiable: its backward was asked to build a graph (create_graph=True), but it has no "
+                           "double backward -- the layer cannot sit under a gradient penalty" % layer)
+
+
+def bn_stats(bn, train: bool, count: int, gamma: Tensor, beta: Tensor, records=None, moments=None):
+    """The statistics of one BatchNorm2d over `count` values: one tensor [4,F] with the rows (scale, shift, invstd, mean), which ctx
+    keeps as it is.  Train mode finalises the batch statistics from records = (partials, tile_rows) of a gather / product pass or from
+    moments = (mean, var), and updates the module's buffers as nn.BatchNorm2d does; eval mode reads the running statistics."""
+    if not train:
+        return ops._bn_prepare4(None, None, gamma, beta, count, False, bn.running_mean, bn.running_var, eps=float(bn.eps))
+    bn.num_batches_tracked += 1
+    if records is not None:
+        return edge_max.edge_max_bn(records[0], records[1], count, gamma, beta, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
+    return ops._bn_prepare4(moments[0], moments[1], gamma, beta, count, True, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
+
+
+def edge_records(PQ: Tensor, idx: Tensor):
+    """The (sum, M2) records of Q_i + P_j over the M*k edges come from edge_max's gather pass; its max / min outputs are dropped"""
+    return edge_max.edge_max_gather(PQ, idx)[4:]
+
+
+def split_records(out, train: bool):
+    """A product launched with stats=train -> (y, its (partials, tile_rows) records | None)"""
+    return (out[0], out[1:]) if train else (out, None)
+
+
+def used(sums: Tensor, train: bool) -> Tensor:
+    """eval mode: the statistics are constants, the BatchNorm backward is the plain scale"""
+    return sums if train else torch.zeros_like(sums)
+
+
+def dbias(rows: Tensor, train: bool) -> Tensor:
+    """a bias in front of a train-mode BatchNorm: exactly zero (the batch mean absorbs it)"""
+    return torch.zeros(rows.shape[1], dtype=torch.float32, device=rows.device) if train else ops.colsum(rows)[0]
+
+
+def gb(sums: Tensor, need, i: int):
+    """sums [2F] = [sum g | sum g*xhat] -> (dgamma, dbeta) for the inputs at positions i, i + 1"""
+    F_ = sums.numel() // 2
+    return (sums[F_:].clone() if need[i] else None, sums[:F_].clone() if need[i + 1] else None)
+
+
+def relu_bn_bwd(dout: Tensor, Y: Tensor, st, gamma: Tensor, h):
+    """The last layer's ReLU + BatchNorm backward: dout [B,F,N] (any view of it), the pre-norm Y [M,F] -> (dy [M,F], sums [2F])"""
+    from . import pointnet_util
+    scale, shift, invstd, mean = st
+    g = ops.cm_to_pm(dout.reshape(h.B, Y.shape[1], h.N).contiguous())
+    r, sums = pointnet_util._group_max_bwd(g, ops.affine_act(Y, scale, shift, 0.0), None, Y, mean, invstd, 0.0, 1)
+    return ops.bn_bwd_apply(r, Y, mean, invstd, gamma, used(sums, h.training), Y.shape[0]), sums
+
+
+def rank_scatter(da: Tensor, rowptr: Tensor, src: Tensor, st, PQ: Tensor, idx: Tensor, sums: Tensor, train: bool) -> Tensor:
+    """da [M,k,F] on the edges -> dPQ [M,2F], through the LeakyReLU'd BatchNorm whose statistics are st"""
+    scale, _, invstd, mean = st
+    if train:
+        return edge_rank.edge_rank_scatter(da, rowptr, src, scale, PQ, idx, mean, invstd, sums)
+    return edge_rank.edge_rank_scatter(da, rowptr, src, scale)
+
+
+# ----------------------------------------------------------------------------- the Functions
+class EdgeMaxConvFn(Function):
+    """out [B,F,N] = max_j relu(bn(conv1x1(cat[x_i, x_j - x_i])))   (the reference's edgeConv, Generation/modules.py:779-796) without the
+    [B,2Fin,N,k] edge tensor: the per-point GEMM and gather passes over it (csrc/edge_max.hip).
+    holder: bn; also receives last_sel, the selected ranks."""
+
+    @staticmethod
+    def forward(ctx, h, x, W, b, gamma, beta):
+        B, Fin, N = x.shape
+        x_pm = ops.cm_to_pm(x)
+        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, h.k, h.knn_mode)
+        Wst = stacked(W)
+        PQ = ops.gemm_nt(x_pm, Wst, pq_bias(b))
+        if h.training:
+            pmax, pmin, rmax, rmin, part, tile_rows = edge_max.edge_max_gather(PQ, idx)
+            st = bn_stats(h.bn, True, idx.numel(), gamma, beta, records=(part, tile_rows))
+            out_pm, sel = edge_max.edge_max_finish(PQ, pmax, pmin, rmax, rmin, st[0], st[1])
+            del pmax, pmin, rmax, rmin
+        else:
+            st = bn_stats(h.bn, False, idx.numel(), gamma, beta)
+            out_pm, sel = edge_max.edge_max_eval(PQ, idx, st[0], st[1])
+        h.last_idx, h.last_sel = idx, sel
+        ctx.h, ctx.st = h, st
+        ctx.save_for_backward(x, PQ, sel, idx, Wst)          # x, not its point-major copy: the input is alive anyway
+        return ops.pm_to_cm(out_pm, B, N)
+
+    @staticmethod
+    def backward(ctx, dout):
+        refuse_double_backward("edgeConv")
+        return EdgeMaxConvFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        x, PQ, sel, idx, Wst = ctx.saved_tensors
+        h = ctx.h
+        scale, _, invstd, mean = ctx.st
+        F_ = sel.shape[1]
+        r = ops.cm_to_pm(dout)                                           # a fresh [M,F] tensor: overwritten with g * 1[out > 0]
+        sums = edge_max.edge_max_bwd_point(r, sel, PQ, idx, mean, invstd)
+        rowptr, src = ops.csr_build(idx, h.B, h.N)
+        if h.training:
+            dPQ = edge_max.edge_max_bwd_graph(r, sel, PQ, h.k, rowptr, src, scale, idx, mean, invstd, sums)
+        else:
+            dPQ = edge_max.edge_max_bwd_graph(r, sel, PQ, h.k, rowptr, src, scale)
+        del r
+        need = ctx.needs_input_grad
+        # dW first: its split-K workspace and the point rows die before dx is made
+        dW = unstacked_grad(ops.gemm_tn(dPQ, ops.cm_to_pm(x))) if need[2] else None
+        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wst.t().contiguous()), h.B, h.N) if need[1] else None
+        db = dbias(dPQ[:, F_:], h.training) if need[3] else None
+        return (None, dx, dW, db) + gb(sums, need, 4)
+
+
+class UpsampleEdgeConvFn(Function):
+    """out [B,Fout,2N] = the reference's upsample_edgeConv (Generation/modules.py:799-845) without the [B,2Fin,N,k] edge tensor, the
+    [B,4Fin,N,k/2] chain behind inte_conv_hk or the merged [B,2Fin,N,2k] tensor: both [1,w] convolutions are products over gathered
+    neighbour rows (csrc/edge_window.hip), their central halves per-point GEMMs, the transpose / view chain a column permutation of
+    conv2's weight (upsample_images), the final view free in a channel-major result.
+    holder: slope, bn1, bn2; parameters of inte_conv_hk, then conv2.  Saved: x, the graph, the pre-norm U [M*T,4Fin] (the one edge-sized
+    tensor), the pre-norm y [M,2Fout] and the statistics."""
+
+    @staticmethod
+    def forward(ctx, h, x, W1, b1, g1, be1, V, b2, g2, be2):
+        B, C, N = x.shape
+        k, M, train = h.k, B * N, h.training
+        T = k - W1.shape[3] + 1
+        x_pm = ops.cm_to_pm(x)
+        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
+        Wc1, Wd1, _, Vc, Vd, _, V2p, _, _, _ = upsample_images(W1, V, C, k)
+        Q1 = ops.gemm_nt(x_pm, Wc1, b1)
+        U, rec = split_records(edge_window.edge_window_gemm(x_pm, idx, Wd1, rowadd=Q1, stats=train), train)
+        st1 = bn_stats(h.bn1, train, M * T, g1, be1, records=rec)
+        del Q1
+        # the activated inte tensor is never stored: BatchNorm + LeakyReLU run in the prologue of the product that consumes it
+        st1r = st1.repeat(1, T)                            # per column t*4C + o of the [M, T*4C] view
+        Y3 = ops.gemm_nt(U.view(M, T * 4 * C), V2p, pro=(st1r[0], st1r[1], h.slope))
+        Q2 = ops.gemm_nt(x_pm, Vc, b2)
+        Y, rec = split_records(edge_window.edge_window_gemm(x_pm, idx, Vd, rowadd=Q2, add2=Y3, stats=train), train)
+        st2 = bn_stats(h.bn2, train, M, g2, be2, records=rec)
+        del Q2, Y3
+        out_pm = ops.affine_act(Y, st2[0], st2[1], 0.0)
+        h.last_idx = idx
+        ctx.h, ctx.st1, ctx.st2, ctx.st1r = h, st1, st2, st1r
+        ctx.save_for_backward(x, U, Y, idx, W1, V, g1, g2)
+        return ops.pm_to_cm(out_pm, B, N).view(B, V.shape[0] // 2, 2 * N)          # out[b, f, s*N + n] = y[b, 2f+s, n]: a view
+
+    @staticmethod
+    def backward(ctx, dout):
+        refuse_double_backward("upsample_edgeConv")
+        return UpsampleEdgeConvFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        x, U, Y, idx, W1, V, g1, g2 = ctx.saved_tensors
+        h = ctx.h
+        B, C, N = x.shape
+        k, M, train = h.k, B * N, h.training
+        w = W1.shape[3]
+        T = k - w + 1
+        F2 = V.shape[0]
+        _, _, inv1, mu1 = ctx.st1
+        sc1r, sh1r, inv1r, mu1r = ctx.st1r
+        need = ctx.needs_input_grad
+        Wc1, Wd1, Wd1t, Vc, Vd, Vdt, V2p, V2pt, Wc1t, Vct = upsample_images(W1, V, C, k)
+        x_pm = ops.cm_to_pm(x)
+        dy, sums2 = relu_bn_bwd(dout, Y, ctx.st2, g2, h)
+        Uf = U.view(M, T * 4 * C)
+        dV = None
+        if need[6]:
+            dV = torch.empty_like(V)
+            dV[:, :C, 0, :k] = ops.gemm_tn(dy, x_pm).unsqueeze(2)
+            dV[:, C:, 0, :k] = edge_window.edge_window_wgrad(x_pm, idx, dy, k).view(F2, k, C).permute(0, 2, 1)
+            dV[:, :, 0, k:] = ops.gemm_tn(dy, Uf, pro=(sc1r, sh1r, h.slope)).view(F2, T, 4 * C).permute(0, 2, 1).reshape(F2, 2 * C, k)
+        # LeakyReLU + BatchNorm of inte_conv_hk: the mask and the column sums come out of the product's epilogue
+        gz, t1, t2 = ops.gemm_nt_bnbwd(dy, V2pt, Uf, sc1r, sh1r, mu1r, inv1r, h.slope)
+        sums1 = torch.cat([t1.view(T, 4 * C).sum(dim=0), t2.view(T, 4 * C).sum(dim=0)])
+        dU = ops.bn_bwd_apply(gz.view(M * T, 4 * C), U, mu1, inv1, g1, used(sums1, train), M * T)
+        del gz
+        dQ1 = ops.colsum(dU, T)                                            # [M,4C]: the central half sees the sum over the window positions
+        dW1 = None
+        if need[2]:
+            dW1 = torch.empty_like(W1)
+            dW1[:, :C, 0, :] = ops.gemm_tn(dQ1, x_pm).unsqueeze(2)
+            dW1[:, C:, 0, :] = edge_window.edge_window_wgrad(x_pm, idx, dU, w).view(4 * C, w, C).permute(0, 2, 1)
+        dx = None
+        if need[1]:
+            S = edge_window.edge_window_dgrad(dU, Wd1t, k, C)              # [M,k,C]: the only per-edge tensor made here
+            edge_window.edge_window_dgrad(dy, Vdt, k, C, out=S)
+            rowptr, src = ops.csr_build(idx, B, N)
+            dx_pm = edge_window.edge_window_scatter(S, rowptr, src, ops.gemm_nt(dy, Vct), ops.gemm_nt(dQ1, Wc1t))
+            del S
+            dx = ops.pm_to_cm(dx_pm, B, N)
+        db1 = dbias(dU, train) if need[3] else None
+        db2 = dbias(dy, train) if need[7] else None
+        return (None, dx, dW1, db1) + gb(sums1, need, 4) + (dV, db2) + gb(sums2, need, 8)
+
+
+class RankEdgeConvFn(Function):
+    """out [B,Fout,N] = relu(bn2(conv[1,k](lrelu(bn1(conv1x1(cat[x_i, x_j - x_i]))))))   (the reference's deform_edgeConv_simple /
+    deform_edgeConv_first, Generation/modules.py:1394-1466) without the [B,2Fin,N,k] edge tensor or the activated [B,F1,N,k] tensor in
+    forward: the per-point GEMM, the first BatchNorm's statistics from edge_max's gather pass over PQ, and the [1,k] convolution as a
+    product with K = k*F1 whose A operand is formed in LDS (csrc/edge_rank.hip).
+    holder: slope, bn1, bn2; parameters of inte_conv_hk, then conv2.  Saved: x, PQ, the pre-norm y [M,Fout], the graph and the
+    statistics; the backward holds one per-edge buffer, da [M,k,F1]."""
+
+    @staticmethod
+    def forward(ctx, h, x, W1, b1, g1, be1, W2, b2, g2, be2):
+        B, Fin, N = x.shape
+        k, M, train = h.k, B * N, h.training
+        x_pm = ops.cm_to_pm(x)
+        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
+        Wst, _, W2i, _ = rank_images(W1, W2)
+        PQ = ops.gemm_nt(x_pm, Wst, pq_bias(b1))
+        st1 = bn_stats(h.bn1, train, M * k, g1, be1, records=edge_records(PQ, idx) if train else None)
+        Y, rec = split_records(edge_rank.edge_rank_gemm(PQ, idx, st1[0], st1[1], W2i, b2, stats=train, slope=h.slope), train)
+        st2 = bn_stats(h.bn2, train, M, g2, be2, records=rec)
+        del rec
+        out_pm = ops.affine_act(Y, st2[0], st2[1], 0.0)
+        h.last_idx = idx
+        ctx.h, ctx.st1, ctx.st2 = h, st1, st2
+        ctx.save_for_backward(x, PQ, Y, idx, W1, W2, g2)
+        return ops.pm_to_cm(out_pm, B, N)
+
+    @staticmethod
+    def backward(ctx, dout):
+        refuse_double_backward("deform_edgeConv")
+        return RankEdgeConvFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        x, PQ, Y, idx, W1, W2, g2 = ctx.saved_tensors
+        h = ctx.h
+        B, Fin, N = x.shape
+        k, train = h.k, h.training
+        F1, Fout = W1.shape[0], W2.shape[0]
+        sc1, sh1, inv1, mu1 = ctx.st1
+        need = ctx.needs_input_grad
+        Wst, Wstt, W2i, W2t = rank_images(W1, W2)
+        dy, sums2 = relu_bn_bwd(dout, Y, ctx.st2, g2, h)
+        # LeakyReLU + BatchNorm of inte_conv_hk: da [M,k,F1] is the only per-edge tensor of the layer
+        da, sums1 = edge_rank.edge_rank_dgrad(dy, W2t, PQ, idx, sc1, sh1, mu1, inv1, h.slope)
+        rowptr, src = ops.csr_build(idx, B, N)
+        dPQ = rank_scatter(da, rowptr, src, ctx.st1, PQ, idx, sums1, train)
+        del da
+        dW2 = None
+        if need[6]:                                                      # after da has died: its split workspace is not held beside da
+            dW2 = edge_rank.edge_rank_wgrad(PQ, idx, sc1, sh1, dy, h.slope).view(Fout, k, F1).permute(0, 2, 1).unsqueeze(2).contiguous()
+        dW1 = unstacked_grad(ops.gemm_tn(dPQ, ops.cm_to_pm(x))) if need[2] else None
+        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wstt), B, N) if need[1] else None
+        db1 = dbias(dPQ[:, F1:], train) if need[3] else None
+        db2 = dbias(dy, train) if need[7] else None
+        return (None, dx, dW1, db1) + gb(sums1, need, 4) + (dW2, db2) + gb(sums2, need, 8)
+
+
+class WeightedRankEdgeConvFn(Function):
+    """out [B,Fout,N] = relu(bn_c(conv[1,k](h * s)))   (the reference's deform_edgeConv_feat, Generation/modules.py:1543-1599) with
+    h = lrelu(bn_h(conv1x1(e))), s = softmax over the k ranks of the shared three-layer MLP conv_fea(e) (or the MLP's output itself with
+    softmax=False) and e = cat[x_i, x_j - x_i], without e, h, s or h*s in memory, forward or backward.
+    Both first layers are per-point GEMMs (PQ_h [M,2Fin], PQ_1 [M,32], statistics from edge_max's gather pass); the MLP's narrow rows
+    z1 [M*k,16], z2 [M*k,64] and its pre-norm output z3 [M*k,Fin] (the one edge-sized tensor of the forward) are stored; the [1,k]
+    convolution forms h*s in LDS from gathered rows of PQ_h, z3 and the per-(point, channel) softmax normaliser (csrc/edge_rank.hip,
+    spgan.edge_weight).  The backward holds two further edge-sized buffers: du and g3 / dz3.
+    holder: softmax, slope, bns = the five nn.BatchNorm2d modules (h, 1, 2, 3, c); parameters of inte_conv_hk, conv_fea.0/1,
+    conv_fea.3/4, conv_fea.6/7 and conv2."""
+
+    @staticmethod
+    def forward(ctx, h, x, *params):
+        Wh, bh, gh, beh, Wf1, bf1, g1, be1, Wf2, bf2, g2, be2, Wf3, bf3, g3, be3, W2, b2, gc, bec = params
+        B, Fin, N = x.shape
+        k, M, train = h.k, B * N, h.training
+        E = M * k
+        x_pm = ops.cm_to_pm(x)
+        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
+        Wst_h, Wst_1, _, Wm2, _, Wm3, _, W2i, _ = weight_images(Wh, Wf1, Wf2, Wf3, W2)
+        # exact=True: fp32 operands whatever ops.set_mfma_operands selected
+        PQh = ops.gemm_nt(x_pm, Wst_h, pq_bias(bh), exact=True)
+        PQ1 = ops.gemm_nt(x_pm, Wst_1, pq_bias(bf1), exact=True)
+        sth = bn_stats(h.bns[0], train, E, gh, beh, records=edge_records(PQh, idx) if train else None)
+        st1 = bn_stats(h.bns[1], train, E, g1, be1, records=edge_records(PQ1, idx) if train else None)
+        z1 = edge_weight.edge_weight_gather(PQ1, idx)
+        if train:
+            z2, m, v = ops.gemm_nt(z1, Wm2, bf2, pro=(st1[0], st1[1], h.slope), stats=True, exact=True)
+            st2 = bn_stats(h.bns[2], True, E, g2, be2, moments=(m, v))
+            z3, m, v = ops.gemm_nt(z2, Wm3, bf3, pro=(st2[0], st2[1], h.slope), stats=True, exact=True)
+            st3 = bn_stats(h.bns[3], True, E, g3, be3, moments=(m, v))
+        else:
+            st2 = bn_stats(h.bns[2], False, E, g2, be2)
+            z2 = ops.gemm_nt(z1, Wm2, bf2, pro=(st1[0], st1[1], h.slope), exact=True)
+            st3 = bn_stats(h.bns[3], False, E, g3, be3)
+            z3 = ops.gemm_nt(z2, Wm3, bf3, pro=(st2[0], st2[1], h.slope), exact=True)
+        norm = edge_weight.edge_weight_norm(z3, k, st3[0], st3[1], h.slope) if h.softmax else None
+        Y, rec = split_records(edge_weight.edge_weight_gemm(PQh, idx, sth[0], sth[1], z3, st3[0], st3[1], norm, W2i, b2, stats=train, slope=h.slope),
+                               train)
+        stc = bn_stats(h.bns[4], train, M, gc, bec, records=rec)
+        del rec
+        out_pm = ops.affine_act(Y, stc[0], stc[1], 0.0)
+        h.last_idx = idx
+        ctx.h, ctx.st, ctx.norm = h, (sth, st1, st2, st3, stc), norm
+        ctx.save_for_backward(x, PQh, PQ1, z1, z2, z3, Y, idx, Wh, Wf1, Wf2, Wf3, W2, g2, g3, gc)
+        return ops.pm_to_cm(out_pm, B, N)
+
+    @staticmethod
+    def backward(ctx, dout):
+        refuse_double_backward("deform_edgeConv_feat")
+        return WeightedRankEdgeConvFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        x, PQh, PQ1, z1, z2, z3, Y, idx, Wh, Wf1, Wf2, Wf3, W2, g2, g3, gc = ctx.saved_tensors
+        h = ctx.h
+        B, Fin, N = x.shape
+        k, M, train = h.k, B * N, h.training
+        E = M * k
+        Fout, F1, Fm = W2.shape[0], Wf1.shape[0], Wf2.shape[0]
+        sth, st1, (sc2, sh2, inv2, mu2), (sc3, sh3, inv3, mu3), stc = ctx.st
+        (sch, shh, invh, muh), (sc1, sh1, inv1, mu1) = sth, st1
+        need = ctx.needs_input_grad
+        _, _, Wall_t, _, Wm2t, _, Wm3t, _, W2t = weight_images(Wh, Wf1, Wf2, Wf3, W2)
+        dy, sumsc = relu_bn_bwd(dout, Y, stc, gc, h)
+        # the product h*s, both LeakyReLUs and the softmax: du and g3 [M,k,Fin] are the two per-edge buffers of the backward
+        du, sumsh, gz3, sums3 = edge_weight.edge_weight_dgrad(dy, W2t, PQh, idx, sch, shh, muh, invh, z3, sc3, sh3, mu3, inv3, ctx.norm, h.slope)
+        rowptr, src = ops.csr_build(idx, B, N)
+        dPQh = rank_scatter(du, rowptr, src, sth, PQh, idx, sumsh, train)
+        del du
+        # the weight MLP, last layer first
+        dz3 = ops.bn_bwd_apply(gz3, z3, mu3, inv3, g3, used(sums3, train), E)
+        del gz3
+        dWf3 = ops.gemm_tn(dz3, z2, pro=(sc2, sh2, h.slope), exact=True).view(Fin, Fm, 1, 1) if need[14] else None
+        dbf3 = dbias(dz3, train) if need[15] else None
+        gz2, t1, t2 = ops.gemm_nt_bnbwd(dz3, Wm3t, z2, sc2, sh2, mu2, inv2, h.slope, exact=True)
+        del dz3
+        sums2 = torch.cat([t1, t2])
+        dz2 = ops.bn_bwd_apply(gz2, z2, mu2, inv2, g2, used(sums2, train), E)
+        del gz2
+        dWf2 = ops.gemm_tn(dz2, z1, pro=(sc1, sh1, h.slope), exact=True).view(Fm, F1, 1, 1) if need[10] else None
+        dbf2 = dbias(dz2, train) if need[11] else None
+        gz1, t1, t2 = ops.gemm_nt_bnbwd(dz2, Wm2t, z1, sc1, sh1, mu1, inv1, h.slope, exact=True)
+        del dz2
+        sums1 = torch.cat([t1, t2])
+        dPQ1 = rank_scatter(gz1.view(M, k, F1), rowptr, src, st1, PQ1, idx, sums1, train)
+        del gz1
+        dW2 = None
+        if need[18]:                                                     # after du and g3 have died: its split workspace is not held beside them
+            dW2 = edge_weight.edge_weight_wgrad(PQh, idx, sch, shh, z3, sc3, sh3, ctx.norm, dy, h.slope)
+            dW2 = dW2.view(Fout, k, Fin).permute(0, 2, 1).unsqueeze(2).contiguous()
+        dPQ = torch.cat([dPQh, dPQ1], dim=1)                             # [M, 2Fin + 32]: both branches feed one product pair
+        dWh = dWf1 = None
+        if need[2] or need[6]:
+            dWst = ops.gemm_tn(dPQ, ops.cm_to_pm(x), exact=True)         # rows of dW'_P, then of dW'_Q, per branch
+            dWh, dWf1 = unstacked_grad(dWst[:2 * Fin]), unstacked_grad(dWst[2 * Fin:])
+        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wall_t, exact=True), B, N) if need[1] else None
+        dbh = dbias(dPQh[:, Fin:], train) if need[3] else None
+        dbf1 = dbias(dPQ1[:, F1:], train) if need[7] else None
+        db2 = dbias(dy, train) if need[19] else None
+        return (None, dx, dWh, dbh) + gb(sumsh, need, 4) + (dWf1, dbf1) + gb(sums1, need, 8) + (dWf2, dbf2) + gb(sums2, need, 12) + \
+            (dWf3, dbf3) + gb(sums3, need, 16) + (dW2, db2) + gb(sumsc, need, 20)

@@ -1,5 +1,5 @@
 """Tensor-level wrappers of the max-aggregation edge convolution's launchers (csrc/edge_max.hip; include/spgan_hip.h): the passes
-behind `spgan.edgeConv` (functions.EdgeMaxConvFn).  PQ [M,2F] = [P | Q] is the per-point GEMM's result, idx int32 [M,k] global rows.
+behind `spgan.edgeConv` (edge_conv.EdgeMaxConvFn).  PQ [M,2F] = [P | Q] is the per-point GEMM's result, idx int32 [M,k] global rows.
 Same conventions as spgan.ops: arguments validated, outputs from PyTorch's caching allocator, launches on the current stream."""
 from __future__ import annotations
 
@@ -19,6 +19,14 @@ def _pq(PQ: Tensor, F_: int) -> Tensor:
     if not PQ.is_contiguous() or PQ.shape[1] != 2 * F_:
         raise ValueError("PQ must be contiguous [M, 2F]")
     return PQ
+
+
+def tile_sums(part: Tensor, M_: int, tile_points: int) -> Tensor:
+    """A backward pass's per-tile records, partials [tiles,F,2] over M points in tiles of tile_points -> sums [2F] = [sum | sum * xhat]"""
+    tiles, F_ = part.shape[0], part.shape[1]
+    sums = torch.empty((2, F_), dtype=torch.float32, device=part.device)
+    check(_lib.load().spgan_colstats_finalize(_p(part), 1, tiles, F_, M_, 1, tile_points, _p(sums[0]), _p(sums[1]), _s()), "colstats_finalize")
+    return sums.view(-1)
 
 
 def edge_max_gather(PQ: Tensor, idx: Tensor):
@@ -81,13 +89,10 @@ def edge_max_bwd_point(g: Tensor, sel: Tensor, PQ: Tensor, idx: Tensor, mean: Te
         raise ValueError("g must be contiguous [M,F] and sel uint8 of the same shape")
     lib = _lib.load()
     tp = lib.spgan_edge_max_tile_points()
-    tiles = (M_ + tp - 1) // tp
-    part = torch.empty((tiles, F_, 2), dtype=torch.float32, device=g.device)
+    part = torch.empty(((M_ + tp - 1) // tp, F_, 2), dtype=torch.float32, device=g.device)
     check(lib.spgan_edge_max_bwd_point(_p(g), _p(sel), _p(PQ), 2 * F_, _p(idx), M_, idx.shape[1], F_, _p(_vec(mean, F_, "mean")),
                                        _p(_vec(invstd, F_, "invstd")), _p(part), _s()), "edge_max_bwd_point", M=M_, F=F_)
-    sums = torch.empty((2, F_), dtype=torch.float32, device=g.device)
-    check(lib.spgan_colstats_finalize(_p(part), 1, tiles, F_, M_, 1, tp, _p(sums[0]), _p(sums[1]), _s()), "colstats_finalize")
-    return sums.view(-1)
+    return tile_sums(part, M_, tp)
 
 
 def edge_max_bwd_graph(r: Tensor, sel: Tensor, PQ: Tensor, k: int, rowptr: Tensor, src: Tensor, scale: Tensor, idx: Optional[Tensor] = None,

@@ -1,5 +1,5 @@
 """Tensor-level wrappers of the rank-window edge convolution's launchers (csrc/edge_window.hip; include/spgan_hip.h): the passes behind
-`spgan.upsample_edgeConv` (functions.UpsampleEdgeConvFn).  x [M,C] point-major, idx int32 [M,k] global rows, W [O, w*C] the difference
+`spgan.upsample_edgeConv` (edge_conv.UpsampleEdgeConvFn).  x [M,C] point-major, idx int32 [M,k] global rows, W [O, w*C] the difference
 half of a [1,w] conv weight, tap-major; T = k - w + 1 window positions per point, output rows (i,t).
 Same conventions as spgan.ops: arguments validated, outputs from PyTorch's caching allocator, launches on the current stream."""
 from __future__ import annotations

@@ -7,15 +7,14 @@ Common/gradient_penalty.py:31-35) by exposing its backward as a second Function.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import List, Optional, Sequence
 
 import threading
 
 import torch
 from torch.autograd import Function
-from torch.autograd.function import once_differentiable
 
-from . import edge_max, edge_rank, edge_weight, edge_window, nets, ops
+from . import nets, ops
 
 Tensor = torch.Tensor
 
@@ -537,531 +536,6 @@ class EdgeBlockFn(Function):
                 cache["csr"] = csr
         dx, g = nets.edgeblock_backward(P, h.prefix, ctx.ectx, dout, csr, need_dx=ctx.needs_input_grad[1])
         return (None, dx) + _deliver(params, [g[n] for n in h.names], ctx.needs_input_grad[2:], ctx.fused)
-
-
-class EdgeMaxConvFn(Function):
-    """out [B,F,N] = max_j relu(bn(conv1x1(cat[x_i, x_j - x_i])))   (the reference's edgeConv, Generation/modules.py:779-796) without the
-    [B,2Fin,N,k] edge tensor: one per-point GEMM PQ = x.[Wd ; Wc - Wd]^T + [0 ; b] and gather passes over it (csrc/edge_max.hip).
-    inputs: holder(B, N, k, training, idx | None, knn_mode, bn = the nn.BatchNorm2d module), x [B,Fin,N], conv weight [F,2Fin,1,1], conv bias,
-    bn weight, bn bias.  Once differentiable: the selection of the max is piecewise constant and the backward is a closed form over
-    saved statistics, so a second derivative through it is refused (no GradientPenalty on top of this layer)."""
-
-    @staticmethod
-    def forward(ctx, h, x, W, b, gamma, beta):
-        B, Fin, N = x.shape
-        F_ = W.shape[0]
-        bn = h.bn
-        x_pm = ops.cm_to_pm(x)
-        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, h.k, h.knn_mode)
-        W2 = W.reshape(F_, 2 * Fin)
-        Wd = W2[:, Fin:]
-        Wst = torch.cat([Wd, W2[:, :Fin] - Wd], dim=0)                   # [2F, Fin]: rows of P, then rows of Q
-        PQ = ops.gemm_nt(x_pm, Wst, torch.cat([torch.zeros_like(b), b]))
-        if h.training:
-            pmax, pmin, rmax, rmin, part, tile_rows = edge_max.edge_max_gather(PQ, idx)
-            st = edge_max.edge_max_bn(part, tile_rows, idx.numel(), gamma, beta, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
-            bn.num_batches_tracked += 1
-            out_pm, sel = edge_max.edge_max_finish(PQ, pmax, pmin, rmax, rmin, st[0], st[1])
-            del pmax, pmin, rmax, rmin
-        else:
-            st = ops.bn_prepare(None, None, gamma, beta, idx.numel(), False, bn.running_mean, bn.running_var, eps=float(bn.eps))
-            out_pm, sel = edge_max.edge_max_eval(PQ, idx, st[0], st[1])
-        h.last_idx, h.last_sel = idx, sel
-        # st (scale, shift, invstd, mean) is made here and handed to nobody else: nothing can write it between forward and backward, so it
-        # rides on ctx like the other Functions' statistics (ctx.bns of the shared MLP) instead of through save_for_backward's version
-        # check.  The running statistics that ARE updated in place above are not read by the backward.
-        ctx.h, ctx.Fin, ctx.st = h, Fin, (st[0], st[1], st[2], st[3])
-        ctx.save_for_backward(x, PQ, sel, idx, Wst)          # x, not its point-major copy: the input is alive anyway
-        return ops.pm_to_cm(out_pm, B, N)
-
-    @staticmethod
-    def backward(ctx, dout):
-        # @once_differentiable alone fails late and only when the cotangent carries a graph; with create_graph=True and a plain cotangent
-        # (autograd.grad(out.sum(), x, create_graph=True): the gradient-penalty pattern) it would hand back a gradient without a graph and
-        # the penalty's second derivative would silently be missing.  Refuse where the request is made.
-        if torch.is_grad_enabled():
-            raise RuntimeError("edgeConv is once differentiable: its backward was asked to build a graph (create_graph=True), but it has no "
-                               "double backward -- the layer cannot sit under a gradient penalty")
-        return EdgeMaxConvFn._backward(ctx, dout)
-
-    @staticmethod
-    @once_differentiable
-    def _backward(ctx, dout):
-        x, PQ, sel, idx, Wst = ctx.saved_tensors
-        h, Fin = ctx.h, ctx.Fin
-        scale, _, invstd, mean = ctx.st
-        F_ = sel.shape[1]
-        r = ops.cm_to_pm(dout)                                           # a fresh [M,F] tensor: overwritten with g * 1[out > 0]
-        sums = edge_max.edge_max_bwd_point(r, sel, PQ, idx, mean, invstd)
-        rowptr, src = ops.csr_build(idx, h.B, h.N)
-        if h.training:
-            dPQ = edge_max.edge_max_bwd_graph(r, sel, PQ, h.k, rowptr, src, scale, idx, mean, invstd, sums)
-        else:
-            dPQ = edge_max.edge_max_bwd_graph(r, sel, PQ, h.k, rowptr, src, scale)
-        del r
-        need = ctx.needs_input_grad
-        dW = None
-        if need[2]:                                                      # first: its split-K workspace and the point rows die before dx is made
-            dWst = ops.gemm_tn(dPQ, ops.cm_to_pm(x))                     # [2F, Fin]: rows of dW'_P, then of dW'_Q
-            dW = torch.cat([dWst[F_:], dWst[:F_] - dWst[F_:]], dim=1).view(F_, 2 * Fin, 1, 1)       # dWc = dW'_Q, dWd = dW'_P - dW'_Q
-        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wst.t().contiguous()), h.B, h.N) if need[1] else None
-        db = None
-        if need[3]:
-            # a bias in front of a train-mode BatchNorm: sum dQ is exactly zero (the batch mean absorbs it)
-            db = torch.zeros(F_, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dPQ[:, F_:])[0]
-        return None, dx, dW, db, (sums[F_:].clone() if need[4] else None), (sums[:F_].clone() if need[5] else None)
-
-
-_UPSAMPLE_IMAGES: Dict[tuple, tuple] = {}
-
-
-def upsample_images(W1: Tensor, V: Tensor, C: int, k: int):
-    """The operand images of upsample_edgeConv's two conv weights (W1 [4C,2C,1,w], V [F2,2C,1,2k]):
-    (Wc1 [4C,C], Wd1 [4C,w*C], Wd1^T, Vc [F2,C], Vd [F2,k*C], Vd^T, V2p [F2,T*4C], V2p^T, Wc1^T, Vc^T).
-    Wc = the central halves summed over the taps; Wd = the difference halves, tap-major; V2p = conv2's last k taps with the columns
-    permuted from the reference's per-point (2C, k) reading, c'*k + j = o*T + t, to this layer's row order t*4C + o.
-    Cached per weight pair until a weight changes (torch's version counter, or an optimiser step of spgan.optim.Adam: the staleness rule
-    of nets._t).  Inside a capture the cache is neither read nor written: the images are rebuilt there, so that their kernels are part
-    of the graph and every replay sees the weights of that moment."""
-    def build():
-        w = W1.shape[3]
-        T = k - w + 1
-        F2 = V.shape[0]
-        Wc1 = W1[:, :C, 0, :].sum(dim=2)
-        Wd1 = W1[:, C:, 0, :].permute(0, 2, 1).reshape(4 * C, w * C)
-        Vc = V[:, :C, 0, :k].sum(dim=2)
-        Vd = V[:, C:, 0, :k].permute(0, 2, 1).reshape(F2, k * C)
-        V2p = V[:, :, 0, k:].reshape(F2, 4 * C, T).permute(0, 2, 1).reshape(F2, T * 4 * C)
-        return (Wc1, Wd1, Wd1.t().contiguous(), Vc, Vd, Vd.t().contiguous(), V2p, V2p.t().contiguous(), Wc1.t().contiguous(),
-                Vc.t().contiguous())
-    W1, V = W1.detach(), V.detach()
-    if ops.capturing():
-        return build()
-    key = (W1.data_ptr(), V.data_ptr(), tuple(W1.shape), tuple(V.shape), C, k)
-    stamp = (ops.weights_epoch_of(W1), ops.weights_epoch_of(V), W1._version, V._version)
-    hit = _UPSAMPLE_IMAGES.get(key)
-    if hit is not None and hit[0] == stamp:
-        return hit[1]
-    if len(_UPSAMPLE_IMAGES) >= 64:
-        _UPSAMPLE_IMAGES.clear()
-    img = build()
-    _UPSAMPLE_IMAGES[key] = (stamp, img)
-    return img
-
-
-class UpsampleEdgeConvFn(Function):
-    """out [B,Fout,2N] = the reference's upsample_edgeConv (Generation/modules.py:799-845) without the [B,2Fin,N,k] edge tensor, the
-    [B,4Fin,N,k/2] chain behind inte_conv_hk or the merged [B,2Fin,N,2k] tensor: both [1,w] convolutions are products over gathered
-    neighbour rows (csrc/edge_window.hip), their central halves per-point GEMMs, the transpose / view chain a column permutation of
-    conv2's weight (upsample_images), the final view free in a channel-major result.
-    inputs: holder(B, N, k, training, idx | None, knn_mode, slope, bn1, bn2 = the nn.BatchNorm2d modules), x [B,Fin,N], then
-    inte_conv_hk's conv weight, conv bias, bn weight, bn bias and conv2's.  Saved: x, the graph, the pre-norm U [M*T,4Fin] (the one
-    edge-sized tensor), the pre-norm y [M,2Fout] and the statistics.  Once differentiable, as EdgeMaxConvFn."""
-
-    @staticmethod
-    def forward(ctx, h, x, W1, b1, g1, be1, V, b2, g2, be2):
-        B, C, N = x.shape
-        k, M = h.k, B * N
-        T = k - W1.shape[3] + 1
-        bn1, bn2 = h.bn1, h.bn2
-        x_pm = ops.cm_to_pm(x)
-        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
-        Wc1, Wd1, _, Vc, Vd, _, V2p, _, _, _ = upsample_images(W1, V, C, k)
-        Q1 = ops.gemm_nt(x_pm, Wc1, b1)
-        if h.training:
-            U, part, rows = edge_window.edge_window_gemm(x_pm, idx, Wd1, rowadd=Q1, stats=True)
-            st1 = edge_max.edge_max_bn(part, rows, M * T, g1, be1, bn1.running_mean, bn1.running_var, float(bn1.momentum), float(bn1.eps))
-            bn1.num_batches_tracked += 1
-        else:
-            U = edge_window.edge_window_gemm(x_pm, idx, Wd1, rowadd=Q1)
-            st1 = ops.bn_prepare(None, None, g1, be1, M * T, False, bn1.running_mean, bn1.running_var, eps=float(bn1.eps))
-        del Q1
-        # the activated inte tensor is never stored: BatchNorm + LeakyReLU run in the prologue of the product that consumes it
-        st1r = (st1 if isinstance(st1, Tensor) else torch.stack(list(st1))).repeat(1, T)         # per column t*4C + o of the [M, T*4C] view
-        Y3 = ops.gemm_nt(U.view(M, T * 4 * C), V2p, pro=(st1r[0], st1r[1], h.slope))
-        Q2 = ops.gemm_nt(x_pm, Vc, b2)
-        if h.training:
-            Y, part, rows = edge_window.edge_window_gemm(x_pm, idx, Vd, rowadd=Q2, add2=Y3, stats=True)
-            st2 = edge_max.edge_max_bn(part, rows, M, g2, be2, bn2.running_mean, bn2.running_var, float(bn2.momentum), float(bn2.eps))
-            bn2.num_batches_tracked += 1
-        else:
-            Y = edge_window.edge_window_gemm(x_pm, idx, Vd, rowadd=Q2, add2=Y3)
-            st2 = ops.bn_prepare(None, None, g2, be2, M, False, bn2.running_mean, bn2.running_var, eps=float(bn2.eps))
-        del Q2, Y3
-        out_pm = ops.affine_act(Y, st2[0], st2[1], 0.0)
-        h.last_idx = idx
-        # the statistics are made here and handed to nobody else: they ride on ctx (see EdgeMaxConvFn)
-        ctx.h, ctx.st1, ctx.st2, ctx.st1r = h, tuple(st1[i] for i in range(4)), tuple(st2[i] for i in range(4)), st1r
-        ctx.save_for_backward(x, U, Y, idx, W1, V, g1, g2)
-        return ops.pm_to_cm(out_pm, B, N).view(B, V.shape[0] // 2, 2 * N)          # out[b, f, s*N + n] = y[b, 2f+s, n]: a view
-
-    @staticmethod
-    def backward(ctx, dout):
-        if torch.is_grad_enabled():
-            raise RuntimeError("upsample_edgeConv is once differentiable: its backward was asked to build a graph (create_graph=True), but "
-                               "it has no double backward -- the layer cannot sit under a gradient penalty")
-        return UpsampleEdgeConvFn._backward(ctx, dout)
-
-    @staticmethod
-    @once_differentiable
-    def _backward(ctx, dout):
-        from . import pointnet_util
-        x, U, Y, idx, W1, V, g1, g2 = ctx.saved_tensors
-        h = ctx.h
-        B, C, N = x.shape
-        k, M = h.k, B * N
-        w = W1.shape[3]
-        T = k - w + 1
-        F2 = V.shape[0]
-        sc1, sh1, inv1, mu1 = ctx.st1
-        sc2, sh2, inv2, mu2 = ctx.st2
-        need = ctx.needs_input_grad
-        Wc1, Wd1, Wd1t, Vc, Vd, Vdt, V2p, V2pt, Wc1t, Vct = upsample_images(W1, V, C, k)
-        x_pm = ops.cm_to_pm(x)
-        # ReLU + BatchNorm of conv2
-        g = ops.cm_to_pm(dout.reshape(B, F2, N).contiguous())
-        r, sums2 = pointnet_util._group_max_bwd(g, ops.affine_act(Y, sc2, sh2, 0.0), None, Y, mu2, inv2, 0.0, 1)
-        dy = ops.bn_bwd_apply(r, Y, mu2, inv2, g2, sums2 if h.training else torch.zeros_like(sums2), M)
-        del g, r
-        Uf = U.view(M, T * 4 * C)
-        sc1r, sh1r, inv1r, mu1r = ctx.st1r[0], ctx.st1r[1], ctx.st1r[2], ctx.st1r[3]
-        dV = None
-        if need[6]:
-            dV = torch.empty_like(V)
-            dV[:, :C, 0, :k] = ops.gemm_tn(dy, x_pm).unsqueeze(2)
-            dV[:, C:, 0, :k] = edge_window.edge_window_wgrad(x_pm, idx, dy, k).view(F2, k, C).permute(0, 2, 1)
-            dV[:, :, 0, k:] = ops.gemm_tn(dy, Uf, pro=(sc1r, sh1r, h.slope)).view(F2, T, 4 * C).permute(0, 2, 1).reshape(F2, 2 * C, k)
-        # LeakyReLU + BatchNorm of inte_conv_hk: the mask and the column sums come out of the product's epilogue
-        gz, t1, t2 = ops.gemm_nt_bnbwd(dy, V2pt, Uf, sc1r, sh1r, mu1r, inv1r, h.slope)
-        sums1 = torch.cat([t1.view(T, 4 * C).sum(dim=0), t2.view(T, 4 * C).sum(dim=0)])
-        dU = ops.bn_bwd_apply(gz.view(M * T, 4 * C), U, mu1, inv1, g1, sums1 if h.training else torch.zeros_like(sums1), M * T)
-        del gz
-        dQ1 = ops.colsum(dU, T)                                            # [M,4C]: the central half sees the sum over the window positions
-        dW1 = None
-        if need[2]:
-            dW1 = torch.empty_like(W1)
-            dW1[:, :C, 0, :] = ops.gemm_tn(dQ1, x_pm).unsqueeze(2)
-            dW1[:, C:, 0, :] = edge_window.edge_window_wgrad(x_pm, idx, dU, w).view(4 * C, w, C).permute(0, 2, 1)
-        dx = None
-        if need[1]:
-            S = edge_window.edge_window_dgrad(dU, Wd1t, k, C)              # [M,k,C]: the only per-edge tensor made here
-            edge_window.edge_window_dgrad(dy, Vdt, k, C, out=S)
-            rowptr, src = ops.csr_build(idx, B, N)
-            dx_pm = edge_window.edge_window_scatter(S, rowptr, src, ops.gemm_nt(dy, Vct), ops.gemm_nt(dQ1, Wc1t))
-            del S
-            dx = ops.pm_to_cm(dx_pm, B, N)
-        # a bias in front of a train-mode BatchNorm: exactly zero (the batch mean absorbs it)
-        db1 = db2 = None
-        if need[3]:
-            db1 = torch.zeros(4 * C, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dU)[0]
-        if need[7]:
-            db2 = torch.zeros(F2, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dy)[0]
-        return (None, dx, dW1, db1, sums1[4 * C:].clone() if need[4] else None, sums1[:4 * C].clone() if need[5] else None,
-                dV, db2, sums2[F2:].clone() if need[8] else None, sums2[:F2].clone() if need[9] else None)
-
-
-_RANK_IMAGES: Dict[tuple, tuple] = {}
-
-
-def rank_images(W1: Tensor, W2: Tensor):
-    """The operand images of the full-rank edge convolution's two conv weights (W1 [F1,2Fin,1,1], W2 [Fout,F1,1,k]):
-    (Wst [2F1,Fin] = [Wd ; Wc - Wd] (rows of P, then of Q), Wst^T, W2i [Fout, k*F1] tap-major (column r*F1 + c), W2i^T).
-    Cached per weight pair under the staleness rule of upsample_images; inside a capture the images are rebuilt."""
-    def build():
-        F1, Fin = W1.shape[0], W1.shape[1] // 2
-        Wm = W1.reshape(F1, 2 * Fin)
-        Wd = Wm[:, Fin:]
-        Wst = torch.cat([Wd, Wm[:, :Fin] - Wd], dim=0)
-        W2i = W2[:, :, 0, :].permute(0, 2, 1).reshape(W2.shape[0], W2.shape[3] * F1)
-        return Wst, Wst.t().contiguous(), W2i, W2i.t().contiguous()
-    W1, W2 = W1.detach(), W2.detach()
-    if ops.capturing():
-        return build()
-    key = (W1.data_ptr(), W2.data_ptr(), tuple(W1.shape), tuple(W2.shape))
-    stamp = (ops.weights_epoch_of(W1), ops.weights_epoch_of(W2), W1._version, W2._version)
-    hit = _RANK_IMAGES.get(key)
-    if hit is not None and hit[0] == stamp:
-        return hit[1]
-    if len(_RANK_IMAGES) >= 64:
-        _RANK_IMAGES.clear()
-    img = build()
-    _RANK_IMAGES[key] = (stamp, img)
-    return img
-
-
-class RankEdgeConvFn(Function):
-    """out [B,Fout,N] = relu(bn2(conv[1,k](lrelu(bn1(conv1x1(cat[x_i, x_j - x_i]))))))   (the reference's deform_edgeConv_simple /
-    deform_edgeConv_first, Generation/modules.py:1394-1466) without the [B,2Fin,N,k] edge tensor or the activated [B,F1,N,k] tensor in
-    forward: one per-point GEMM PQ = x.[Wd ; Wc - Wd]^T + [0 ; b1], the first BatchNorm's statistics from edge_max's gather pass over PQ, and
-    the [1,k] convolution as a product with K = k*F1 whose A operand is formed in LDS (csrc/edge_rank.hip).
-    inputs: holder(B, N, k, training, idx | None, knn_mode, slope, bn1, bn2 = the nn.BatchNorm2d modules), x [B,Fin,N], then
-    inte_conv_hk's conv weight, conv bias, bn weight, bn bias and conv2's.  Saved: x, PQ, the pre-norm y [M,Fout], the graph and the
-    statistics; the backward holds one per-edge buffer, da [M,k,F1].  Once differentiable, as EdgeMaxConvFn."""
-
-    @staticmethod
-    def forward(ctx, h, x, W1, b1, g1, be1, W2, b2, g2, be2):
-        B, Fin, N = x.shape
-        k, M = h.k, B * N
-        bn1, bn2 = h.bn1, h.bn2
-        x_pm = ops.cm_to_pm(x)
-        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
-        Wst, _, W2i, _ = rank_images(W1, W2)
-        PQ = ops.gemm_nt(x_pm, Wst, torch.cat([torch.zeros_like(b1), b1]))
-        if h.training:
-            # the (sum, M2) records of Q_i + P_j over the M*k edges come from edge_max's gather pass; its max / min outputs are dropped
-            part = edge_max.edge_max_gather(PQ, idx)[4:]
-            st1 = edge_max.edge_max_bn(part[0], part[1], M * k, g1, be1, bn1.running_mean, bn1.running_var, float(bn1.momentum), float(bn1.eps))
-            bn1.num_batches_tracked += 1
-            Y, part, rows = edge_rank.edge_rank_gemm(PQ, idx, st1[0], st1[1], W2i, b2, stats=True, slope=h.slope)
-            st2 = edge_max.edge_max_bn(part, rows, M, g2, be2, bn2.running_mean, bn2.running_var, float(bn2.momentum), float(bn2.eps))
-            bn2.num_batches_tracked += 1
-            del part
-        else:
-            st1 = ops.bn_prepare(None, None, g1, be1, M * k, False, bn1.running_mean, bn1.running_var, eps=float(bn1.eps))
-            Y = edge_rank.edge_rank_gemm(PQ, idx, st1[0], st1[1], W2i, b2, slope=h.slope)
-            st2 = ops.bn_prepare(None, None, g2, be2, M, False, bn2.running_mean, bn2.running_var, eps=float(bn2.eps))
-        out_pm = ops.affine_act(Y, st2[0], st2[1], 0.0)
-        h.last_idx = idx
-        # the statistics are made here and handed to nobody else: they ride on ctx (see EdgeMaxConvFn)
-        ctx.h, ctx.st1, ctx.st2 = h, tuple(st1[i] for i in range(4)), tuple(st2[i] for i in range(4))
-        ctx.save_for_backward(x, PQ, Y, idx, W1, W2, g2)
-        return ops.pm_to_cm(out_pm, B, N)
-
-    @staticmethod
-    def backward(ctx, dout):
-        if torch.is_grad_enabled():
-            raise RuntimeError("deform_edgeConv is once differentiable: its backward was asked to build a graph (create_graph=True), but "
-                               "it has no double backward -- the layer cannot sit under a gradient penalty")
-        return RankEdgeConvFn._backward(ctx, dout)
-
-    @staticmethod
-    @once_differentiable
-    def _backward(ctx, dout):
-        from . import pointnet_util
-        x, PQ, Y, idx, W1, W2, g2 = ctx.saved_tensors
-        h = ctx.h
-        B, Fin, N = x.shape
-        k, M = h.k, B * N
-        F1, Fout = W1.shape[0], W2.shape[0]
-        sc1, sh1, inv1, mu1 = ctx.st1
-        sc2, sh2, inv2, mu2 = ctx.st2
-        need = ctx.needs_input_grad
-        Wst, Wstt, W2i, W2t = rank_images(W1, W2)
-        # ReLU + BatchNorm of conv2
-        g = ops.cm_to_pm(dout.contiguous())
-        r, sums2 = pointnet_util._group_max_bwd(g, ops.affine_act(Y, sc2, sh2, 0.0), None, Y, mu2, inv2, 0.0, 1)
-        dy = ops.bn_bwd_apply(r, Y, mu2, inv2, g2, sums2 if h.training else torch.zeros_like(sums2), M)
-        del g, r
-        # LeakyReLU + BatchNorm of inte_conv_hk: da [M,k,F1] is the only per-edge tensor of the layer
-        da, sums1 = edge_rank.edge_rank_dgrad(dy, W2t, PQ, idx, sc1, sh1, mu1, inv1, h.slope)
-        rowptr, src = ops.csr_build(idx, B, N)
-        if h.training:
-            dPQ = edge_rank.edge_rank_scatter(da, rowptr, src, sc1, PQ, idx, mu1, inv1, sums1)
-        else:
-            dPQ = edge_rank.edge_rank_scatter(da, rowptr, src, sc1)
-        del da
-        dW2 = None
-        if need[6]:                                                      # after da has died: its split workspace is not held beside da
-            dW2 = edge_rank.edge_rank_wgrad(PQ, idx, sc1, sh1, dy, h.slope).view(Fout, k, F1).permute(0, 2, 1).unsqueeze(2).contiguous()
-        dW1 = None
-        if need[2]:
-            dWst = ops.gemm_tn(dPQ, ops.cm_to_pm(x))                     # [2F1, Fin]: rows of dW'_P, then of dW'_Q
-            dW1 = torch.cat([dWst[F1:], dWst[:F1] - dWst[F1:]], dim=1).view(F1, 2 * Fin, 1, 1)      # dWc = dW'_Q, dWd = dW'_P - dW'_Q
-        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wstt), B, N) if need[1] else None
-        # a bias in front of a train-mode BatchNorm: exactly zero (the batch mean absorbs it)
-        db1 = db2 = None
-        if need[3]:
-            db1 = torch.zeros(F1, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dPQ[:, F1:])[0]
-        if need[7]:
-            db2 = torch.zeros(Fout, dtype=torch.float32, device=dout.device) if h.training else ops.colsum(dy)[0]
-        return (None, dx, dW1, db1, sums1[F1:].clone() if need[4] else None, sums1[:F1].clone() if need[5] else None,
-                dW2, db2, sums2[Fout:].clone() if need[8] else None, sums2[:Fout].clone() if need[9] else None)
-
-
-_WEIGHT_IMAGES: Dict[tuple, tuple] = {}
-
-
-def weight_images(Wh: Tensor, Wf1: Tensor, Wf2: Tensor, Wf3: Tensor, W2: Tensor):
-    """The operand images of deform_edgeConv_feat's five conv weights (inte_conv_hk.0 [Fin,2Fin,1,1], conv_fea.0 [16,2Fin,1,1], conv_fea.3
-    [64,16,1,1], conv_fea.6 [Fin,64,1,1], conv2.conv [Fout,Fin,1,k]):
-    (Wst_h [2Fin,Fin] and Wst_1 [32,Fin] = [Wd ; Wc - Wd] of the two per-point GEMMs, Wall_t [Fin, 2Fin+32] = their stack transposed,
-    Wm2 [64,16], Wm2^T, Wm3 [Fin,64], Wm3^T, W2i [Fout, k*Fin] tap-major, W2i^T).
-    Cached per weight set under the staleness rule of rank_images; inside a capture the images are rebuilt."""
-    def build():
-        def stack(W):
-            F_, C = W.shape[0], W.shape[1] // 2
-            Wm = W.reshape(F_, 2 * C)
-            return torch.cat([Wm[:, C:], Wm[:, :C] - Wm[:, C:]], dim=0)
-        Wst_h, Wst_1 = stack(Wh), stack(Wf1)
-        Wm2, Wm3 = Wf2.reshape(Wf2.shape[0], Wf2.shape[1]), Wf3.reshape(Wf3.shape[0], Wf3.shape[1])
-        W2i = W2[:, :, 0, :].permute(0, 2, 1).reshape(W2.shape[0], W2.shape[3] * W2.shape[1])
-        return (Wst_h, Wst_1, torch.cat([Wst_h, Wst_1], dim=0).t().contiguous(), Wm2.contiguous(), Wm2.t().contiguous(), Wm3.contiguous(),
-                Wm3.t().contiguous(), W2i, W2i.t().contiguous())
-    ws = tuple(w.detach() for w in (Wh, Wf1, Wf2, Wf3, W2))
-    Wh, Wf1, Wf2, Wf3, W2 = ws
-    if ops.capturing():
-        return build()
-    key = tuple(w.data_ptr() for w in ws) + tuple(tuple(w.shape) for w in ws)
-    stamp = tuple(ops.weights_epoch_of(w) for w in ws) + tuple(w._version for w in ws)
-    hit = _WEIGHT_IMAGES.get(key)
-    if hit is not None and hit[0] == stamp:
-        return hit[1]
-    if len(_WEIGHT_IMAGES) >= 64:
-        _WEIGHT_IMAGES.clear()
-    img = build()
-    _WEIGHT_IMAGES[key] = (stamp, img)
-    return img
-
-
-class WeightedRankEdgeConvFn(Function):
-    """out [B,Fout,N] = relu(bn_c(conv[1,k](h * s)))   (the reference's deform_edgeConv_feat, Generation/modules.py:1543-1599) with
-    h = lrelu(bn_h(conv1x1(e))), s = softmax over the k ranks of the shared three-layer MLP conv_fea(e) (or the MLP's output itself with
-    softmax=False) and e = cat[x_i, x_j - x_i], without e, h, s or h*s in memory, forward or backward.
-    Both first layers are per-point GEMMs (PQ_h [M,2Fin], PQ_1 [M,32], statistics from edge_max's gather pass); the MLP's narrow rows
-    z1 [M*k,16], z2 [M*k,64] and its pre-norm output z3 [M*k,Fin] (the one edge-sized tensor of the forward) are stored; the [1,k]
-    convolution forms h*s in LDS from gathered rows of PQ_h, z3 and the per-(point, channel) softmax normaliser (csrc/edge_rank.hip,
-    spgan.edge_weight).  The backward holds two further edge-sized buffers: du and g3 / dz3.
-    inputs: holder(B, N, k, training, softmax, idx | None, knn_mode, slope, bns = the five nn.BatchNorm2d modules (h, 1, 2, 3, c)),
-    x [B,Fin,N], then (conv weight, conv bias, bn weight, bn bias) of inte_conv_hk, conv_fea.0/1, conv_fea.3/4, conv_fea.6/7 and conv2.
-    Once differentiable, as RankEdgeConvFn.  Exact fp32 products: the layer does not follow ops.set_mfma_operands."""
-
-    @staticmethod
-    def forward(ctx, h, x, *params):
-        Wh, bh, gh, beh, Wf1, bf1, g1, be1, Wf2, bf2, g2, be2, Wf3, bf3, g3, be3, W2, b2, gc, bec = params
-        B, Fin, N = x.shape
-        k, M = h.k, B * N
-        E = M * k
-        x_pm = ops.cm_to_pm(x)
-        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
-        Wst_h, Wst_1, _, Wm2, _, Wm3, _, W2i, _ = weight_images(Wh, Wf1, Wf2, Wf3, W2)
-
-        def stats(bn, count, gamma, beta, records=None, moments=None):
-            """(scale, shift, invstd, mean) of one BatchNorm2d; train mode updates its buffers as nn.BatchNorm2d does"""
-            if not h.training:
-                return ops.bn_prepare(None, None, gamma, beta, count, False, bn.running_mean, bn.running_var, eps=float(bn.eps))
-            bn.num_batches_tracked += 1
-            if records is not None:
-                return edge_max.edge_max_bn(records[0], records[1], count, gamma, beta, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
-            return ops.bn_prepare(moments[0], moments[1], gamma, beta, count, True, bn.running_mean, bn.running_var, float(bn.momentum), float(bn.eps))
-
-        # exact=True: fp32 operands whatever ops.set_mfma_operands selected
-        PQh = ops.gemm_nt(x_pm, Wst_h, torch.cat([torch.zeros_like(bh), bh]), exact=True)
-        PQ1 = ops.gemm_nt(x_pm, Wst_1, torch.cat([torch.zeros_like(bf1), bf1]), exact=True)
-        train = h.training
-        # the (sum, M2) records of Q_i + P_j over the M*k edges come from edge_max's gather pass; its max / min outputs are dropped
-        sth = stats(h.bns[0], E, gh, beh, records=edge_max.edge_max_gather(PQh, idx)[4:] if train else None)
-        st1 = stats(h.bns[1], E, g1, be1, records=edge_max.edge_max_gather(PQ1, idx)[4:] if train else None)
-        z1 = edge_weight.edge_weight_gather(PQ1, idx)
-        if train:
-            z2, m, v = ops.gemm_nt(z1, Wm2, bf2, pro=(st1[0], st1[1], h.slope), stats=True, exact=True)
-            st2 = stats(h.bns[2], E, g2, be2, moments=(m, v))
-            z3, m, v = ops.gemm_nt(z2, Wm3, bf3, pro=(st2[0], st2[1], h.slope), stats=True, exact=True)
-            st3 = stats(h.bns[3], E, g3, be3, moments=(m, v))
-        else:
-            st2 = stats(h.bns[2], E, g2, be2)
-            z2 = ops.gemm_nt(z1, Wm2, bf2, pro=(st1[0], st1[1], h.slope), exact=True)
-            st3 = stats(h.bns[3], E, g3, be3)
-            z3 = ops.gemm_nt(z2, Wm3, bf3, pro=(st2[0], st2[1], h.slope), exact=True)
-        norm = edge_weight.edge_weight_norm(z3, k, st3[0], st3[1], h.slope) if h.softmax else None
-        if train:
-            Y, part, rows = edge_weight.edge_weight_gemm(PQh, idx, sth[0], sth[1], z3, st3[0], st3[1], norm, W2i, b2, stats=True, slope=h.slope)
-            stc = stats(h.bns[4], M, gc, bec, records=(part, rows))
-            del part
-        else:
-            Y = edge_weight.edge_weight_gemm(PQh, idx, sth[0], sth[1], z3, st3[0], st3[1], norm, W2i, b2, slope=h.slope)
-            stc = stats(h.bns[4], M, gc, bec)
-        out_pm = ops.affine_act(Y, stc[0], stc[1], 0.0)
-        h.last_idx = idx
-        # the statistics are made here and handed to nobody else: they ride on ctx (see EdgeMaxConvFn)
-        ctx.h = h
-        ctx.st = tuple(tuple(st[i] for i in range(4)) for st in (sth, st1, st2, st3, stc))
-        ctx.norm = norm
-        ctx.save_for_backward(x, PQh, PQ1, z1, z2, z3, Y, idx, Wh, Wf1, Wf2, Wf3, W2, g2, g3, gc)
-        return ops.pm_to_cm(out_pm, B, N)
-
-    @staticmethod
-    def backward(ctx, dout):
-        if torch.is_grad_enabled():
-            raise RuntimeError("deform_edgeConv_feat is once differentiable: its backward was asked to build a graph (create_graph=True), but "
-                               "it has no double backward -- the layer cannot sit under a gradient penalty")
-        return WeightedRankEdgeConvFn._backward(ctx, dout)
-
-    @staticmethod
-    @once_differentiable
-    def _backward(ctx, dout):
-        from . import pointnet_util
-        x, PQh, PQ1, z1, z2, z3, Y, idx, Wh, Wf1, Wf2, Wf3, W2, g2, g3, gc = ctx.saved_tensors
-        h = ctx.h
-        B, Fin, N = x.shape
-        k, M = h.k, B * N
-        E = M * k
-        Fout, F1, Fm = W2.shape[0], Wf1.shape[0], Wf2.shape[0]
-        (sch, shh, invh, muh), (sc1, sh1, inv1, mu1), (sc2, sh2, inv2, mu2), (sc3, sh3, inv3, mu3), (scc, shc, invc, muc) = ctx.st
-        need = ctx.needs_input_grad
-        train = h.training
-        dev = dout.device
-        _, _, Wall_t, _, Wm2t, _, Wm3t, _, W2t = weight_images(Wh, Wf1, Wf2, Wf3, W2)
-
-        def used(sums):                  # eval mode: the statistics are constants, the BatchNorm backward is the plain scale
-            return sums if train else torch.zeros_like(sums)
-
-        def dbias(rows):                 # a bias in front of a train-mode BatchNorm: exactly zero (the batch mean absorbs it)
-            return torch.zeros(rows.shape[1], dtype=torch.float32, device=dev) if train else ops.colsum(rows)[0]
-
-        # ReLU + BatchNorm of conv2
-        g = ops.cm_to_pm(dout.contiguous())
-        r, sumsc = pointnet_util._group_max_bwd(g, ops.affine_act(Y, scc, shc, 0.0), None, Y, muc, invc, 0.0, 1)
-        dy = ops.bn_bwd_apply(r, Y, muc, invc, gc, used(sumsc), M)
-        del g, r
-        # the product h*s, both LeakyReLUs and the softmax: du and g3 [M,k,Fin] are the two per-edge buffers of the backward
-        du, sumsh, gz3, sums3 = edge_weight.edge_weight_dgrad(dy, W2t, PQh, idx, sch, shh, muh, invh, z3, sc3, sh3, mu3, inv3, ctx.norm, h.slope)
-        rowptr, src = ops.csr_build(idx, B, N)
-        if train:
-            dPQh = edge_rank.edge_rank_scatter(du, rowptr, src, sch, PQh, idx, muh, invh, sumsh)
-        else:
-            dPQh = edge_rank.edge_rank_scatter(du, rowptr, src, sch)
-        del du
-        # the weight MLP, last layer first
-        dz3 = ops.bn_bwd_apply(gz3, z3, mu3, inv3, g3, used(sums3), E)
-        del gz3
-        dWf3 = ops.gemm_tn(dz3, z2, pro=(sc2, sh2, h.slope), exact=True).view(Fin, Fm, 1, 1) if need[14] else None
-        dbf3 = dbias(dz3) if need[15] else None
-        gz2, t1, t2 = ops.gemm_nt_bnbwd(dz3, Wm3t, z2, sc2, sh2, mu2, inv2, h.slope, exact=True)
-        del dz3
-        sums2 = torch.cat([t1, t2])
-        dz2 = ops.bn_bwd_apply(gz2, z2, mu2, inv2, g2, used(sums2), E)
-        del gz2
-        dWf2 = ops.gemm_tn(dz2, z1, pro=(sc1, sh1, h.slope), exact=True).view(Fm, F1, 1, 1) if need[10] else None
-        dbf2 = dbias(dz2) if need[11] else None
-        gz1, t1, t2 = ops.gemm_nt_bnbwd(dz2, Wm2t, z1, sc1, sh1, mu1, inv1, h.slope, exact=True)
-        del dz2
-        sums1 = torch.cat([t1, t2])
-        if train:
-            dPQ1 = edge_rank.edge_rank_scatter(gz1.view(M, k, F1), rowptr, src, sc1, PQ1, idx, mu1, inv1, sums1)
-        else:
-            dPQ1 = edge_rank.edge_rank_scatter(gz1.view(M, k, F1), rowptr, src, sc1)
-        del gz1
-        dW2 = None
-        if need[18]:                                                     # after du and g3 have died: its split workspace is not held beside them
-            dW2 = edge_weight.edge_weight_wgrad(PQh, idx, sch, shh, z3, sc3, sh3, ctx.norm, dy, h.slope)
-            dW2 = dW2.view(Fout, k, Fin).permute(0, 2, 1).unsqueeze(2).contiguous()
-        dPQ = torch.cat([dPQh, dPQ1], dim=1)                             # [M, 2Fin + 32]: both branches feed one product pair
-        dWh = dWf1 = None
-        if need[2] or need[6]:
-            dWst = ops.gemm_tn(dPQ, ops.cm_to_pm(x), exact=True)                     # rows of dW'_P, then of dW'_Q, per branch
-
-            def conv_grad(d, F_):                                        # dWc = dW'_Q, dWd = dW'_P - dW'_Q
-                return torch.cat([d[F_:], d[:F_] - d[F_:]], dim=1).view(F_, 2 * Fin, 1, 1)
-            dWh, dWf1 = conv_grad(dWst[:2 * Fin], Fin), conv_grad(dWst[2 * Fin:], F1)
-        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wall_t, exact=True), B, N) if need[1] else None
-        dbh = dbias(dPQh[:, Fin:]) if need[3] else None
-        dbf1 = dbias(dPQ1[:, F1:]) if need[7] else None
-        db2 = dbias(dy) if need[19] else None
-
-        def gb(sums, F_, i):             # (dgamma, dbeta) = (sum g*xhat, sum g)
-            return (sums[F_:].clone() if need[i] else None, sums[:F_].clone() if need[i + 1] else None)
-        return (None, dx, dWh, dbh) + gb(sumsh, Fin, 4) + (dWf1, dbf1) + gb(sums1, F1, 8) + (dWf2, dbf2) + gb(sums2, Fm, 12) + \
-            (dWf3, dbf3) + gb(sums3, Fin, 16) + (dW2, db2) + gb(sumsc, Fout, 20)
 
 
 class EdgeFeaturesFn(Function):

@@ -4,7 +4,7 @@
 The modules own torch.nn layers purely as *parameter containers*: constructed in the reference's
 order, so `state_dict()` keys/shapes and default initial values match and reference checkpoints
 load both ways.  Their `forward` never calls those layers: it runs the HIP pipelines of
-`functions.py` / `nets.py`.  There is no CPU path: inputs must be on the GPU.
+`functions.py` / `edge_conv.py` / `nets.py`.  There is no CPU path: inputs must be on the GPU.
 """
 from __future__ import annotations
 
@@ -15,6 +15,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
+from . import edge_conv
 from . import functions as Fn
 from . import nets, ops
 from .functions import _Holder
@@ -632,9 +633,36 @@ class conv2dbr(nn.Module):
         return out.view(B, H, W, -1).permute(0, 3, 1, 2)
 
 
+def check_edge_input(name: str, x, idx, k: int, Fin: int, Fout: int, bns, unsupported: Optional[str] = None):
+    """The input check of the gather-side edge convolutions (spgan.edge_conv) -> (B, N, idx, knn_mode): x [B,Fin,N] on the GPU, BatchNorm
+    modules that keep running statistics with a momentum, and an injected graph -- int64 [B, N*k] local indices, range-checked outside a
+    capture, are converted to the layers' int32 [B*N,k] global rows; a graph already in that format is trusted.  unsupported: a layer's
+    own refusal of its settings, raised with the BatchNorm refusals (before idx is looked at)."""
+    _require_gpu(x, name)
+    B, C, N = x.shape
+    if C != Fin:
+        raise ValueError("%s(%d, %d, %d) got an input with %d channels" % (name, Fin, Fout, k, C))
+    for bn in bns:
+        if bn.momentum is None or not bn.track_running_stats:
+            raise NotImplementedError("%s: BatchNorm2d with momentum=None or track_running_stats=False is not supported" % name)
+    if unsupported is not None:
+        raise NotImplementedError("%s: %s" % (name, unsupported))
+    if idx is not None:
+        _require_gpu(idx, name + " idx")
+        if idx.dtype == torch.int64:
+            if idx.numel() != B * N * k:
+                raise ValueError("%s: idx must hold B*N*k = %d indices, got %s" % (name, B * N * k, tuple(idx.shape)))
+            if not ops.capturing() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+                raise IndexError("%s: a neighbour index lies outside [0, %d)" % (name, N))
+            idx = ops.idx_from_local64(idx.reshape(B, N * k), B, N, k)
+        elif idx.dtype != torch.int32 or tuple(idx.shape) != (B * N, k):
+            raise ValueError("%s: idx must be int64 [B, N*k] (local) or int32 [B*N, k] (global rows)" % name)
+    return B, N, idx, 1 if Fin <= 4 else 0
+
+
 class edgeConv(nn.Module):
     """Generation/modules.py:779-796: max over the k neighbours of conv2dbr(get_edge_features(x)), [B,Fin,N] -> [B,Fout,N], evaluated per
-    point (Fn.EdgeMaxConvFn): no [B,2Fin,N,k] tensor in forward or backward.  idx (an extension): the graph to use instead of the kNN
+    point (edge_conv.EdgeMaxConvFn): no [B,2Fin,N,k] tensor in forward or backward.  idx (an extension): the graph to use instead of the kNN
     graph of x, int64 [B, N*k] local indices as get_edge_features returns them (or int32 [B*N,k] global rows: the layer's own format, trusted -- only
     int64 graphs are range-checked).  A negative bn.weight
     entry takes the min branch.  Once differentiable.  last_idx / last_sel: the graph and the selected ranks of the latest forward."""
@@ -651,25 +679,10 @@ class edgeConv(nn.Module):
         self.last_sel: Optional[torch.Tensor] = None
 
     def forward(self, x, idx: Optional[torch.Tensor] = None):
-        _require_gpu(x, "edgeConv")
-        B, Fin, N = x.shape
-        if Fin != self.Fin:
-            raise ValueError("edgeConv(%d, %d, %d) got an input with %d channels" % (self.Fin, self.Fout, self.k, Fin))
         bn = self.conv.bn
-        if bn.momentum is None or not bn.track_running_stats:
-            raise NotImplementedError("edgeConv: BatchNorm2d with momentum=None or track_running_stats=False is not supported")
-        if idx is not None:
-            _require_gpu(idx, "edgeConv idx")
-            if idx.dtype == torch.int64:
-                if idx.numel() != B * N * self.k:
-                    raise ValueError("edgeConv: idx must hold B*N*k = %d indices, got %s" % (B * N * self.k, tuple(idx.shape)))
-                if not ops.capturing() and (int(idx.min()) < 0 or int(idx.max()) >= N):
-                    raise IndexError("edgeConv: a neighbour index lies outside [0, %d)" % N)
-                idx = ops.idx_from_local64(idx.reshape(B, N * self.k), B, N, self.k)
-            elif idx.dtype != torch.int32 or tuple(idx.shape) != (B * N, self.k):
-                raise ValueError("edgeConv: idx must be int64 [B, N*k] (local) or int32 [B*N, k] (global rows)")
-        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=1 if Fin <= 4 else 0, bn=bn, last_idx=None, last_sel=None)
-        out = Fn.EdgeMaxConvFn.apply(h, x.contiguous(), self.conv.conv.weight, self.conv.conv.bias, bn.weight, bn.bias)
+        B, N, idx, knn_mode = check_edge_input("edgeConv", x, idx, self.k, self.Fin, self.Fout, (bn,))
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=knn_mode, bn=bn, last_idx=None, last_sel=None)
+        out = edge_conv.EdgeMaxConvFn.apply(h, x.contiguous(), self.conv.conv.weight, self.conv.conv.bias, bn.weight, bn.bias)
         self.last_idx, self.last_sel = h.last_idx, h.last_sel
         return out
 
@@ -689,7 +702,7 @@ def get_edge_features_xyz(x, pc, k, num=-1):
 class upsample_edgeConv(nn.Module):
     """Generation/modules.py:799-845: the point-doubling edge convolution, [B,Fin,N] -> [B,Fout,2N]:
     conv2(cat(ee, reshuffled inte_conv_hk(ee))) with ee = get_edge_features(x), evaluated over gathered neighbour rows
-    (Fn.UpsampleEdgeConvFn, csrc/edge_window.hip): neither ee nor the merged [B,2Fin,N,2k] tensor exists in forward or backward.
+    (edge_conv.UpsampleEdgeConvFn, csrc/edge_window.hip): neither ee nor the merged [B,2Fin,N,2k] tensor exists in forward or backward.
     The sub-modules are parameter containers in the reference's order (state_dicts load strictly both ways); conv2 on its own still
     refuses its [1,2k] kernel.  idx (an extension, as edgeConv's): the graph to use instead of the kNN graph of x, int64 [B, N*k] local
     indices (range-checked outside a capture) or int32 [B*N,k] global rows (trusted).  Once differentiable.  last_idx: the graph of
@@ -714,29 +727,13 @@ class upsample_edgeConv(nn.Module):
         self.last_idx: Optional[torch.Tensor] = None
 
     def forward(self, x, idx: Optional[torch.Tensor] = None):
-        _require_gpu(x, "upsample_edgeConv")
-        B, Fin, N = x.shape
-        if Fin != self.Fin:
-            raise ValueError("upsample_edgeConv(%d, %d, %d) got an input with %d channels" % (self.Fin, self.Fout, self.k, Fin))
         conv1, bn1, act = self.inte_conv_hk[0], self.inte_conv_hk[1], self.inte_conv_hk[2]
         bn2 = self.conv2.bn
-        for bn in (bn1, bn2):
-            if bn.momentum is None or not bn.track_running_stats:
-                raise NotImplementedError("upsample_edgeConv: BatchNorm2d with momentum=None or track_running_stats=False is not supported")
-        if idx is not None:
-            _require_gpu(idx, "upsample_edgeConv idx")
-            if idx.dtype == torch.int64:
-                if idx.numel() != B * N * self.k:
-                    raise ValueError("upsample_edgeConv: idx must hold B*N*k = %d indices, got %s" % (B * N * self.k, tuple(idx.shape)))
-                if not ops.capturing() and (int(idx.min()) < 0 or int(idx.max()) >= N):
-                    raise IndexError("upsample_edgeConv: a neighbour index lies outside [0, %d)" % N)
-                idx = ops.idx_from_local64(idx.reshape(B, N * self.k), B, N, self.k)
-            elif idx.dtype != torch.int32 or tuple(idx.shape) != (B * N, self.k):
-                raise ValueError("upsample_edgeConv: idx must be int64 [B, N*k] (local) or int32 [B*N, k] (global rows)")
-        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=1 if Fin <= 4 else 0, slope=float(act.negative_slope),
+        B, N, idx, knn_mode = check_edge_input("upsample_edgeConv", x, idx, self.k, self.Fin, self.Fout, (bn1, bn2))
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=knn_mode, slope=float(act.negative_slope),
                     bn1=bn1, bn2=bn2, last_idx=None)
-        out = Fn.UpsampleEdgeConvFn.apply(h, x.contiguous(), conv1.weight, conv1.bias, bn1.weight, bn1.bias,
-                                          self.conv2.conv.weight, self.conv2.conv.bias, bn2.weight, bn2.bias)
+        out = edge_conv.UpsampleEdgeConvFn.apply(h, x.contiguous(), conv1.weight, conv1.bias, bn1.weight, bn1.bias,
+                                                 self.conv2.conv.weight, self.conv2.conv.bias, bn2.weight, bn2.bias)
         self.last_idx = h.last_idx
         return out
 
@@ -744,7 +741,7 @@ class upsample_edgeConv(nn.Module):
 class _RankEdgeConv(nn.Module):
     """The shared body of deform_edgeConv_simple / deform_edgeConv_first: conv2(inte_conv_hk(get_edge_features(x))) with
     inte_conv_hk = Conv2d(2Fin -> F1, 1x1) + BatchNorm2d + LeakyReLU and conv2 = conv2dbr(F1 -> Fout, [1,k]), evaluated over gathered rows
-    of one per-point GEMM (Fn.RankEdgeConvFn, csrc/edge_rank.hip): neither the [B,2Fin,N,k] edge tensor nor the activated [B,F1,N,k]
+    of one per-point GEMM (edge_conv.RankEdgeConvFn, csrc/edge_rank.hip): neither the [B,2Fin,N,k] edge tensor nor the activated [B,F1,N,k]
     tensor exists in forward; the backward holds one [B*N,k,F1] buffer.  The sub-modules are parameter containers with the reference's
     names (state_dicts load strictly both ways); conv2 on its own still refuses its [1,k] kernel for k > 1."""
 
@@ -767,30 +764,13 @@ class _RankEdgeConv(nn.Module):
         self.last_idx: Optional[torch.Tensor] = None
 
     def _run(self, x, idx):
-        name = type(self).__name__
-        _require_gpu(x, name)
-        B, Fin, N = x.shape
-        if Fin != self.Fin:
-            raise ValueError("%s(%d, %d, %d) got an input with %d channels" % (name, self.Fin, self.Fout, self.k, Fin))
         conv1, bn1, act = self.inte_conv_hk[0], self.inte_conv_hk[1], self.inte_conv_hk[2]
         bn2 = self.conv2.bn
-        for bn in (bn1, bn2):
-            if bn.momentum is None or not bn.track_running_stats:
-                raise NotImplementedError("%s: BatchNorm2d with momentum=None or track_running_stats=False is not supported" % name)
-        if idx is not None:
-            _require_gpu(idx, name + " idx")
-            if idx.dtype == torch.int64:
-                if idx.numel() != B * N * self.k:
-                    raise ValueError("%s: idx must hold B*N*k = %d indices, got %s" % (name, B * N * self.k, tuple(idx.shape)))
-                if not ops.capturing() and (int(idx.min()) < 0 or int(idx.max()) >= N):
-                    raise IndexError("%s: a neighbour index lies outside [0, %d)" % (name, N))
-                idx = ops.idx_from_local64(idx.reshape(B, N * self.k), B, N, self.k)
-            elif idx.dtype != torch.int32 or tuple(idx.shape) != (B * N, self.k):
-                raise ValueError("%s: idx must be int64 [B, N*k] (local) or int32 [B*N, k] (global rows)" % name)
-        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=1 if Fin <= 4 else 0, slope=float(act.negative_slope),
+        B, N, idx, knn_mode = check_edge_input(type(self).__name__, x, idx, self.k, self.Fin, self.Fout, (bn1, bn2))
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=knn_mode, slope=float(act.negative_slope),
                     bn1=bn1, bn2=bn2, last_idx=None)
-        out = Fn.RankEdgeConvFn.apply(h, x.contiguous(), conv1.weight, conv1.bias, bn1.weight, bn1.bias,
-                                      self.conv2.conv.weight, self.conv2.conv.bias, bn2.weight, bn2.bias)
+        out = edge_conv.RankEdgeConvFn.apply(h, x.contiguous(), conv1.weight, conv1.bias, bn1.weight, bn1.bias,
+                                             self.conv2.conv.weight, self.conv2.conv.bias, bn2.weight, bn2.bias)
         self.last_idx = h.last_idx
         return out
 
@@ -826,7 +806,7 @@ class deform_edgeConv_feat(nn.Module):
     """Generation/modules.py:1543-1599: [B,Fin,N] -> [B,Fout,N], conv2dbr(Fin -> Fout, [1,k]) over inte_conv_hk(e) * w with e =
     get_edge_features(x), inte_conv_hk = Conv2d(2Fin -> Fin, 1x1) + BatchNorm2d + LeakyReLU and w = conv_fea(e), a shared MLP
     2Fin -> 16 -> 64 -> Fin (each Conv2d 1x1 + BatchNorm2d + LeakyReLU), normalised by a softmax over the k neighbours (softmax=True).
-    Evaluated by Fn.WeightedRankEdgeConvFn (csrc/edge_rank.hip): e, the activated tensor, the weight and their product never exist in
+    Evaluated by edge_conv.WeightedRankEdgeConvFn (csrc/edge_rank.hip): e, the activated tensor, the weight and their product never exist in
     memory; the forward keeps one [B*N,k,Fin] tensor, the backward two more.  The sub-modules are parameter containers in the reference's
     order and names (state_dicts load strictly both ways).  idx (an extension, as edgeConv's): the graph to use instead of the kNN graph
     of x, int64 [B, N*k] local indices (range-checked outside a capture) or int32 [B*N,k] global rows (trusted).  1 <= k <= 32.  Once
@@ -863,31 +843,14 @@ class deform_edgeConv_feat(nn.Module):
 
     def forward(self, x, idx: Optional[torch.Tensor] = None):
         name = "deform_edgeConv_feat"
-        _require_gpu(x, name)
-        B, Fin, N = x.shape
-        if Fin != self.Fin:
-            raise ValueError("%s(%d, %d, %d) got an input with %d channels" % (name, self.Fin, self.Fout, self.k, Fin))
         layers = [(self.inte_conv_hk[0], self.inte_conv_hk[1])] + [(self.conv_fea[i], self.conv_fea[i + 1]) for i in (0, 3, 6)] + \
             [(self.conv2.conv, self.conv2.bn)]
-        for _, bn in layers:
-            if bn.momentum is None or not bn.track_running_stats:
-                raise NotImplementedError("%s: BatchNorm2d with momentum=None or track_running_stats=False is not supported" % name)
         slopes = {float(a.negative_slope) for a in (self.inte_conv_hk[2], self.conv_fea[2], self.conv_fea[5], self.conv_fea[8])}
-        if len(slopes) != 1:
-            raise NotImplementedError("%s: the four LeakyReLUs must share one slope, got %s" % (name, sorted(slopes)))
-        if idx is not None:
-            _require_gpu(idx, name + " idx")
-            if idx.dtype == torch.int64:
-                if idx.numel() != B * N * self.k:
-                    raise ValueError("%s: idx must hold B*N*k = %d indices, got %s" % (name, B * N * self.k, tuple(idx.shape)))
-                if not ops.capturing() and (int(idx.min()) < 0 or int(idx.max()) >= N):
-                    raise IndexError("%s: a neighbour index lies outside [0, %d)" % (name, N))
-                idx = ops.idx_from_local64(idx.reshape(B, N * self.k), B, N, self.k)
-            elif idx.dtype != torch.int32 or tuple(idx.shape) != (B * N, self.k):
-                raise ValueError("%s: idx must be int64 [B, N*k] (local) or int32 [B*N, k] (global rows)" % name)
-        h = _Holder(B=B, N=N, k=self.k, training=self.training, softmax=bool(self.softmax), idx=idx, knn_mode=1 if Fin <= 4 else 0,
+        B, N, idx, knn_mode = check_edge_input(name, x, idx, self.k, self.Fin, self.Fout, [bn for _, bn in layers],
+                                               None if len(slopes) == 1 else "the four LeakyReLUs must share one slope, got %s" % sorted(slopes))
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, softmax=bool(self.softmax), idx=idx, knn_mode=knn_mode,
                     slope=slopes.pop(), bns=tuple(bn for _, bn in layers), last_idx=None)
         params = [t for conv, bn in layers for t in (conv.weight, conv.bias, bn.weight, bn.bias)]
-        out = Fn.WeightedRankEdgeConvFn.apply(h, x.contiguous(), *params)
+        out = edge_conv.WeightedRankEdgeConvFn.apply(h, x.contiguous(), *params)
         self.last_idx = h.last_idx
         return out

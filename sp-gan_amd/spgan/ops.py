@@ -1501,6 +1501,14 @@ def bn_prepare(mean: Optional[Tensor], var: Optional[Tensor], gamma: Optional[Te
                training: bool = True, running_mean: Optional[Tensor] = None, running_var: Optional[Tensor] = None,
                momentum: Optional[float] = None, eps: float = BN_EPS):
     """-> (scale, shift, invstd, mean_used) each [C]; updates the running statistics in place (train mode)."""
+    out = _bn_prepare4(mean, var, gamma, beta, count, training, running_mean, running_var, momentum, eps)
+    return out[0], out[1], out[2], out[3]
+
+
+def _bn_prepare4(mean: Optional[Tensor], var: Optional[Tensor], gamma: Optional[Tensor], beta: Optional[Tensor], count: int,
+                training: bool = True, running_mean: Optional[Tensor] = None, running_var: Optional[Tensor] = None,
+                momentum: Optional[float] = None, eps: float = BN_EPS) -> Tensor:
+    """bn_prepare with its result as one tensor [4,C]: rows scale, shift, invstd, mean_used"""
     if momentum is None:
         momentum = _BN_MOM[0]
     ref = mean if mean is not None else running_mean
@@ -1509,7 +1517,7 @@ def bn_prepare(mean: Optional[Tensor], var: Optional[Tensor], gamma: Optional[Te
     check(_lib.load().spgan_bn_prepare(_p(mean), _p(var), _p(gamma), _p(beta), Cn, count, eps, momentum, 1 if training else 0,
                                        _p(running_mean), _p(running_var), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), _s()),
           "bn_prepare", C=Cn)
-    return out[0], out[1], out[2], out[3]
+    return out
 
 
 def bn_bwd_apply(g: Tensor, y: Tensor, mean: Tensor, invstd: Tensor, gamma: Optional[Tensor], sums: Tensor, count: int,
