@@ -781,6 +781,21 @@ int spgan_edge_weight_dgrad(const float* dY, int ldg, const float* W2t, int ldwt
                             int O, const float* scale1, const float* shift1, const float* mean1, const float* invstd1, float slope, const float* z3,
                             const float* scale3, const float* shift3, const float* mean3, const float* invstd3, const float* wmax, const float* wrs,
                             float* dU, float* G3, float* partials_u, float* partials_3, spgan_stream_t s);
+/* Coordinate-guided full-rank edge convolution (csrc/edge_rank.hip): the two passes deform_edgeConv (Generation/modules.py:1468-1540) adds
+ * to the weighted layer above.  Its weight MLP reads the product of two activated branches over the same graph, each a per-point GEMM
+ * PQx [M, ldx >= 2F] = [P | Q] with the affine (scale_x, shift_x) of its BatchNorm: a_x(i,r,c) = lrelu(scale_x[c] * (Qx[i,c] + Px[idx[i,r],c]) + shift_x[c]).
+ *   spgan_edge_weight_gather2: W0[(i*k + r), c] = a_a * a_b   (W0 [M*k, F] contiguous).
+ *   spgan_edge_weight_split:   GA[i,r,c] = lrelu'(pre_a) * dW0 * a_b,  GB[i,r,c] = lrelu'(pre_b) * dW0 * a_a   (dW0, GA, GB [M,k,F] contiguous,
+ *                              GA != GB); partials_x [ceil(M / tile_points)][F][2] = (sum Gx, sum Gx * zhat_x), zhat_x = (Qx + Px - mean_x) *
+ *                              invstd_x, plain sums (finalize mode 1; spgan_edge_rank_scatter takes the reduced sums).  Both passes form a_x
+ *                              with one device function: the backward multiplies with the forward's bits.  No float atomics.
+ * 1 <= k <= 32, any M and F; rows of F % 4 == 0 floats on 16-byte aligned operands move as 16-byte pieces. */
+int spgan_edge_weight_gather2(const float* PQa, int lda, const float* PQb, int ldb, const int32_t* idx, int M, int k, int F, const float* scale_a,
+                              const float* shift_a, const float* scale_b, const float* shift_b, float slope, float* W0, spgan_stream_t s);
+int spgan_edge_weight_split(const float* dW0, const float* PQa, int lda, const float* PQb, int ldb, const int32_t* idx, int M, int k, int F,
+                            const float* scale_a, const float* shift_a, const float* mean_a, const float* invstd_a, const float* scale_b,
+                            const float* shift_b, const float* mean_b, const float* invstd_b, float slope, float* GA, float* GB, float* partials_a,
+                            float* partials_b, spgan_stream_t s);
 /* Per-channel scalar algebra of the double backward, one launch each:
  *   coeffs out4C = [dgammaA | sbarA | xsum0 | xsum1];  phaseb: sums2C = [xsum0+gamma*s0 | xsum1+gamma*s1+invstd*sbarA], dgamma = dgammaA+s1 */
 int spgan_bn_dbl_coeffs(const float* U0, const float* U1, const float* Ugz, const float* S0, const float* S1, const float* gamma,

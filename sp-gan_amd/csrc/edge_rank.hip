@@ -25,6 +25,13 @@
 // the gradients reaching both pre-activation BatchNorm outputs (du, g3) with their column records; spgan_edge_weight_norm writes the
 // softmax normaliser per (point, channel) and spgan_edge_weight_gather the pre-norm rows of the weight MLP's first layer.
 //
+// The coordinate-guided layer (deform_edgeConv, Generation/modules.py:1468-1540) feeds that weight MLP the product of two activated
+// 16-channel branches, one over the features and one over the coordinates, both gathered through the same graph:
+//   spgan_edge_weight_gather2  W0[(i*k + r), c] = a_a * a_b, a_x = lrelu(scale_x * (Qx_i + Px_n(i,r)) + shift_x)   [M*k, F]
+//   spgan_edge_weight_split    GA = lrelu'(pre_a) * dW0 * a_b, GB = lrelu'(pre_b) * dW0 * a_a  [M,k,F] with the per-tile column records
+//                              (sum G, sum G * zhat) of each branch, as spgan_edge_rank_dgrad writes them
+// Both are gather passes over rows of F floats: consecutive lanes take consecutive 16-byte pieces of consecutive edge rows.
+//
 // MFMA operand order as in edge_window.hip: a 16-wide K block is one 16-byte fragment per lane (lane group g = lane>>4 holds K elements
 // 4g..4g+3), consumed by four MFMA steps; A and B agree on that order.  fp32 operands, fp32 accumulation: exact products.
 #include "common.hpp"
@@ -617,6 +624,111 @@ __global__ __launch_bounds__(256) void edge_weight_dgrad_kernel(const float* __r
   }
 }
 
+// ------------------------------------------------------------------------------------------ the coordinate-guided layer's own passes
+// One activated branch value of deform_edgeConv's weight input: both kernels below form it here, so that the a the backward multiplies
+// with is the forward's, bit for bit.
+struct Branch {
+  const float* PQ; int ld; const float* sc; const float* sh; const float* mean; const float* invstd;
+};
+__device__ __forceinline__ float branch_a(float q, float p, float sc, float sh, float slope) { return lrelu_f(pre_act(q, p, sc, sh), slope); }
+
+// one thread per (edge, V channels): W0 = a_a * a_b
+template <int V>
+__global__ __launch_bounds__(256) void edge_weight_gather2_kernel(Branch A, Branch B, const int32_t* __restrict__ idx, int M, int k, int F, float slope,
+                                                                  float* __restrict__ W0) {
+  const int QC = F / V;
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (tid >= (size_t)M * k * QC) return;
+  const int c = (int)(tid % QC) * V;
+  const size_t e = tid / QC;
+  const int i = (int)(e / k), r = (int)(e % k);
+  const int n = neighbour(idx, i, k, r, M);
+  float pa[V], qa[V], pb[V], qb[V], sa[V], ta[V], sb[V], tb[V], w[V];
+  ldv<V>(A.PQ + (size_t)n * A.ld + c, pa); ldv<V>(A.PQ + (size_t)i * A.ld + F + c, qa);
+  ldv<V>(B.PQ + (size_t)n * B.ld + c, pb); ldv<V>(B.PQ + (size_t)i * B.ld + F + c, qb);
+  ldv<V>(A.sc + c, sa); ldv<V>(A.sh + c, ta); ldv<V>(B.sc + c, sb); ldv<V>(B.sh + c, tb);
+#pragma unroll
+  for (int u = 0; u < V; ++u) w[u] = branch_a(qa[u], pa[u], sa[u], ta[u], slope) * branch_a(qb[u], pb[u], sb[u], tb[u], slope);
+  stv<V>(W0 + e * F + c, w);
+}
+
+// A workgroup owns the ER_PT points of one record tile: np*k edge rows.  A thread keeps its V channels for the whole tile and walks the
+// rows in ascending order (256 / QC rows per sweep), so its four sums per channel (sum GA, sum GA*zhat_a, sum GB, sum GB*zhat_b) have a
+// fixed order; the threads of a channel are then combined in a fixed order: by xor shuffles inside a wave where the channel groups divide
+// a wave, through LDS in ascending thread order otherwise.
+template <int V>
+__global__ __launch_bounds__(256) void edge_weight_split_kernel(const float* __restrict__ dW0, Branch A, Branch B, const int32_t* __restrict__ idx, int M,
+                                                                int k, int F, float slope, float* __restrict__ GA, float* __restrict__ GB,
+                                                                float* __restrict__ partA, float* __restrict__ partB) {
+  __shared__ float sm[4 * V * 256];
+  const int bx = xcd_block();
+  const int p0 = bx * ER_PT;
+  if (p0 >= M) return;
+  const int ne = min(ER_PT, M - p0) * k;
+  const size_t e0 = (size_t)p0 * k;
+  const int QC = F / V;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  for (int cb = 0; cb < QC; cb += 256) {
+    const int nq = min(256, QC - cb);
+    const int rows = 256 / nq;                       // edge rows per sweep; the threads past rows * nq idle
+    const bool on = t < rows * nq;
+    const bool pow2 = nq <= 64 && (nq & (nq - 1)) == 0;      // uniform
+    const int c = (cb + t % nq) * V;
+    float sa[V], ta[V], ma[V], ia[V], sb[V], tb[V], mb[V], ib[V], acc[4][V];
+#pragma unroll
+    for (int u = 0; u < V; ++u) acc[0][u] = acc[1][u] = acc[2][u] = acc[3][u] = 0.f;
+    if (on) {
+      ldv<V>(A.sc + c, sa); ldv<V>(A.sh + c, ta); ldv<V>(A.mean + c, ma); ldv<V>(A.invstd + c, ia);
+      ldv<V>(B.sc + c, sb); ldv<V>(B.sh + c, tb); ldv<V>(B.mean + c, mb); ldv<V>(B.invstd + c, ib);
+      for (int el = t / nq; el < ne; el += rows) {
+        const int i = p0 + el / k;
+        const int n = neighbour(idx, i, k, el % k, M);
+        const size_t e = e0 + el;
+        float d[V], pa[V], qa[V], pb[V], qb[V], ga[V], gb[V];
+        ldv<V>(dW0 + e * F + c, d);
+        ldv<V>(A.PQ + (size_t)n * A.ld + c, pa); ldv<V>(A.PQ + (size_t)i * A.ld + F + c, qa);
+        ldv<V>(B.PQ + (size_t)n * B.ld + c, pb); ldv<V>(B.PQ + (size_t)i * B.ld + F + c, qb);
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+          const float aa = branch_a(qa[u], pa[u], sa[u], ta[u], slope), ab = branch_a(qb[u], pb[u], sb[u], tb[u], slope);
+          ga[u] = lrelu_mask(pre_act(qa[u], pa[u], sa[u], ta[u]), slope) * d[u] * ab;
+          gb[u] = lrelu_mask(pre_act(qb[u], pb[u], sb[u], tb[u]), slope) * d[u] * aa;
+          acc[0][u] += ga[u];
+          acc[1][u] = fmaf(ga[u], ((qa[u] + pa[u]) - ma[u]) * ia[u], acc[1][u]);
+          acc[2][u] += gb[u];
+          acc[3][u] = fmaf(gb[u], ((qb[u] + pb[u]) - mb[u]) * ib[u], acc[3][u]);
+        }
+        stv<V>(GA + e * F + c, ga);
+        stv<V>(GB + e * F + c, gb);
+      }
+    }
+    int slot = t, groups = rows;
+    if (pow2) {                                      // every thread is on: the lanes of a channel group are lane, lane + nq, ...
+      for (int off = nq; off < 64; off <<= 1)
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+#pragma unroll
+          for (int u = 0; u < V; ++u) acc[v][u] += __shfl_xor(acc[v][u], off);
+      slot = lane < nq ? wave * nq + lane : -1;
+      groups = 4;
+    }
+    __syncthreads();                                 // the previous channel block's records have been read
+    if (slot >= 0)
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int u = 0; u < V; ++u) sm[(v * V + u) * 256 + slot] = on ? acc[v][u] : 0.f;
+    __syncthreads();
+    for (int o = t; o < nq * 4 * V; o += 256) {
+      const int j = o % nq, vu = o / nq;
+      float s = 0.f;
+      for (int g = 0; g < groups; ++g) s += sm[vu * 256 + g * nq + j];
+      const int v = vu / V, ch = (cb + j) * V + vu % V;
+      ((v < 2 ? partA : partB) + ((size_t)bx * F + ch) * 2)[v & 1] = s;
+    }
+  }
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool sizes_ok(int M, int k, int F1, int O) {
   return M > 0 && k >= 1 && k <= ER_KMAX && F1 > 0 && O > 0 && (long)M * k <= 0x7fffffffL && (long)k * F1 <= 0x7fffffffL;
@@ -773,5 +885,35 @@ extern "C" int spgan_edge_weight_dgrad(const float* dY, int ldg, const float* W2
   else
     hipLaunchKernelGGL(edge_weight_dgrad_kernel<false>, gr, b, 0, st, dY, ldg, W2t, ldwt, PQ, ld, idx, M, k, F1, O, scale1, shift1, mean1, invstd1, slope, md,
                        mean3, invstd3, dU, G3, partials_u, partials_3);
+  return spgan_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------ the coordinate-guided layer (deform_edgeConv)
+extern "C" int spgan_edge_weight_gather2(const float* PQa, int lda, const float* PQb, int ldb, const int32_t* idx, int M, int k, int F,
+                                         const float* scale_a, const float* shift_a, const float* scale_b, const float* shift_b, float slope,
+                                         float* W0, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(PQa && PQb && idx && scale_a && shift_a && scale_b && shift_b && W0 && sizes_ok(M, k, F, 1) && lda >= 2 * F && ldb >= 2 * F);
+  SPGAN_CHECK_ARG((long)M * k * F <= 0x7fffffffL * 256L);
+  const Branch A{PQa, lda, scale_a, shift_a, nullptr, nullptr}, B{PQb, ldb, scale_b, shift_b, nullptr, nullptr};
+  const bool v4 = F % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && al16(PQa) && al16(PQb) && al16(scale_a) && al16(shift_a) && al16(scale_b) &&
+                  al16(shift_b) && al16(W0);
+  const long items = (long)M * k * (v4 ? F / 4 : F);
+  if (v4) hipLaunchKernelGGL(edge_weight_gather2_kernel<4>, dim3(cdiv(items, 256)), dim3(256), 0, (hipStream_t)s_, A, B, idx, M, k, F, slope, W0);
+  else hipLaunchKernelGGL(edge_weight_gather2_kernel<1>, dim3(cdiv(items, 256)), dim3(256), 0, (hipStream_t)s_, A, B, idx, M, k, F, slope, W0);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_edge_weight_split(const float* dW0, const float* PQa, int lda, const float* PQb, int ldb, const int32_t* idx, int M, int k, int F,
+                                       const float* scale_a, const float* shift_a, const float* mean_a, const float* invstd_a, const float* scale_b,
+                                       const float* shift_b, const float* mean_b, const float* invstd_b, float slope, float* GA, float* GB,
+                                       float* partials_a, float* partials_b, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(dW0 && PQa && PQb && idx && scale_a && shift_a && mean_a && invstd_a && scale_b && shift_b && mean_b && invstd_b);
+  SPGAN_CHECK_ARG(GA && GB && GA != GB && partials_a && partials_b && partials_a != partials_b && sizes_ok(M, k, F, 1) && lda >= 2 * F && ldb >= 2 * F);
+  const Branch A{PQa, lda, scale_a, shift_a, mean_a, invstd_a}, B{PQb, ldb, scale_b, shift_b, mean_b, invstd_b};
+  const bool v4 = F % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && al16(dW0) && al16(PQa) && al16(PQb) && al16(GA) && al16(GB) && al16(scale_a) &&
+                  al16(shift_a) && al16(mean_a) && al16(invstd_a) && al16(scale_b) && al16(shift_b) && al16(mean_b) && al16(invstd_b);
+  const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
+  if (v4) hipLaunchKernelGGL(edge_weight_split_kernel<4>, gr, b, 0, (hipStream_t)s_, dW0, A, B, idx, M, k, F, slope, GA, GB, partials_a, partials_b);
+  else hipLaunchKernelGGL(edge_weight_split_kernel<1>, gr, b, 0, (hipStream_t)s_, dW0, A, B, idx, M, k, F, slope, GA, GB, partials_a, partials_b);
   return spgan_launch_status();
 }

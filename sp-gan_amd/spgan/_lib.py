@@ -300,6 +300,8 @@ SIGNATURES = {
     "spgan_edge_weight_gemm": (I, [P, I, P, I, I, I, P, P, F, P, P, P, P, P, P, I, P, I, P, I, P, P]),
     "spgan_edge_weight_wgrad": (I, [P, I, P, I, I, I, P, P, F, P, P, P, P, P, P, I, I, P, I, P, SZ, P]),
     "spgan_edge_weight_dgrad": (I, [P, I, P, I, P, I, P, I, I, I, I, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "spgan_edge_weight_gather2": (I, [P, I, P, I, P, I, I, I, P, P, P, P, F, P, P]),
+    "spgan_edge_weight_split": (I, [P, P, I, P, I, P, I, I, I, P, P, P, P, P, P, P, P, F, P, P, P, P, P]),
     "spgan_nn_distance": (I, [P, P, I, I, I, P, P, P]),
     "spgan_chamfer_bwd": (I, [P, P, I, I, I, P, P, P, P, P, P]),
     "spgan_chamfer_pairs": (I, [P, P, I, I, I, I, P, P]),

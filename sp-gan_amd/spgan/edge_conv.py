@@ -1,5 +1,5 @@
 """The gather-side edge convolutions: the autograd Functions behind `spgan.edgeConv`, `upsample_edgeConv`, `deform_edgeConv_simple` /
-`_first` and `deform_edgeConv_feat`, over the launchers of spgan.edge_max / edge_window / edge_rank / edge_weight.
+`_first`, `deform_edgeConv_feat` and `deform_edgeConv`, over the launchers of spgan.edge_max / edge_window / edge_rank / edge_weight.
 
 The family's conventions, stated once:
 * A 1x1 convolution over the edge features cat[x_i, x_j - x_i] is one per-point GEMM, PQ [M,2F] = [P | Q] = x.[Wd ; Wc - Wd]^T + [0 ; b]
@@ -12,7 +12,7 @@ The family's conventions, stated once:
   statistics that ARE updated in place are not read by the backward.
 * Once differentiable: a selection or a mask is piecewise constant and the backward is a closed form over saved statistics, so a second
   derivative is refused where it is asked for (`refuse_double_backward`): no GradientPenalty on top of these layers.
-* The rank layers (RankEdgeConvFn's [1,k] product, all of WeightedRankEdgeConvFn) compute exact fp32 products: they do not follow
+* The rank layers (RankEdgeConvFn's [1,k] product, all of WeightedRankEdgeConvFn and CoordRankEdgeConvFn) compute exact fp32 products: they do not follow
   ops.set_mfma_operands.
 * Weight-derived operand images are cached per weight set (`cached_images`)."""
 from __future__ import annotations
@@ -30,7 +30,7 @@ Tensor = torch.Tensor
 
 # ----------------------------------------------------------------------------- operand images
 # one dictionary per builder: a layer that reaches the cap does not evict another layer's images
-_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}}
+_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}, "coord": {}}
 
 
 def cached_images(cache: Dict[tuple, tuple], weights: Sequence[Tensor], extra: tuple, build: Callable):
@@ -118,6 +118,21 @@ def weight_images(Wh: Tensor, Wf1: Tensor, Wf2: Tensor, Wf3: Tensor, W2: Tensor)
     return cached_images(_IMAGES["weight"], (Wh, Wf1, Wf2, Wf3, W2), (), build)
 
 
+def coord_images(Wh: Tensor, Wf: Tensor, Wx: Tensor, Wa2: Tensor, Wa3: Tensor, W2: Tensor):
+    """The operand images of deform_edgeConv's six conv weights (inte_conv_hk.0 [Fin,2Fin,1,1], conv_fea.0 [16,2Fin,1,1], conv_xyz.0 [16,6,1,1],
+    conv_all.0 [64,16,1,1], conv_all.3 [Fin,64,1,1], conv2.0 [Fout,Fin,1,k]):
+    (Wst_h [2Fin,Fin], Wst_f [32,Fin] and Wst_x [32,3] = [Wd ; Wc - Wd] of the three per-point GEMMs, Wall_t [Fin, 2Fin+32] = the two
+    feature-side stacks transposed, Wst_x^T [3,32], Wm2 [64,16], Wm2^T, Wm3 [Fin,64], Wm3^T, W2i [Fout, k*Fin] tap-major, W2i^T).
+    Cached per weight set (cached_images)."""
+    def build(Wh, Wf, Wx, Wa2, Wa3, W2):
+        Wst_h, Wst_f, Wst_x = stacked(Wh), stacked(Wf), stacked(Wx)
+        Wm2, Wm3 = Wa2.reshape(Wa2.shape[0], Wa2.shape[1]), Wa3.reshape(Wa3.shape[0], Wa3.shape[1])
+        W2i = W2[:, :, 0, :].permute(0, 2, 1).reshape(W2.shape[0], W2.shape[3] * W2.shape[1])
+        return (Wst_h, Wst_f, Wst_x, torch.cat([Wst_h, Wst_f], dim=0).t().contiguous(), Wst_x.t().contiguous(), Wm2.contiguous(), Wm2.t().contiguous(),
+                Wm3.contiguous(), Wm3.t().contiguous(), W2i, W2i.t().contiguous())
+    return cached_images(_IMAGES["coord"], (Wh, Wf, Wx, Wa2, Wa3, W2), (), build)
+
+
 # ----------------------------------------------------------------------------- what the Functions share
 def refuse_double_backward(layer: str) -> None:
     """First line of every backward.  @once_differentiable alone fails late and only when the cotangent carries a graph; with
@@ -168,10 +183,16 @@ def gb(sums: Tensor, need, i: int):
 
 def relu_bn_bwd(dout: Tensor, Y: Tensor, st, gamma: Tensor, h):
     """The last layer's ReLU + BatchNorm backward: dout [B,F,N] (any view of it), the pre-norm Y [M,F] -> (dy [M,F], sums [2F])"""
+    return lrelu_bn_bwd(dout, Y, st, gamma, h, 0.0)
+
+
+def lrelu_bn_bwd(dout: Tensor, Y: Tensor, st, gamma: Tensor, h, slope: float):
+    """relu_bn_bwd for a last layer that ends in LeakyReLU(slope).  With one row per group the pooling backward is the per-row mask: it
+    multiplies by 1 where the activated value is positive and by `slope` elsewhere, and the activated value has the pre-activation's sign."""
     from . import pointnet_util
     scale, shift, invstd, mean = st
     g = ops.cm_to_pm(dout.reshape(h.B, Y.shape[1], h.N).contiguous())
-    r, sums = pointnet_util._group_max_bwd(g, ops.affine_act(Y, scale, shift, 0.0), None, Y, mean, invstd, 0.0, 1)
+    r, sums = pointnet_util._group_max_bwd(g, ops.affine_act(Y, scale, shift, slope), None, Y, mean, invstd, slope, 1)
     return ops.bn_bwd_apply(r, Y, mean, invstd, gamma, used(sums, h.training), Y.shape[0]), sums
 
 
@@ -483,3 +504,120 @@ class WeightedRankEdgeConvFn(Function):
         db2 = dbias(dy, train) if need[19] else None
         return (None, dx, dWh, dbh) + gb(sumsh, need, 4) + (dWf1, dbf1) + gb(sums1, need, 8) + (dWf2, dbf2) + gb(sums2, need, 12) + \
             (dWf3, dbf3) + gb(sums3, need, 16) + (dW2, db2) + gb(sumsc, need, 20)
+
+
+class CoordRankEdgeConvFn(Function):
+    """out [B,Fout,N] = lrelu(bn_c(conv[1,k](h * s)))   (the reference's deform_edgeConv, Generation/modules.py:1468-1540): the weighted layer
+    above with the weight MLP fed by w0 = a_f * a_x, a_f = lrelu(bn_f(conv_fea(e))) over e = cat[x_i, x_j - x_i] and a_x =
+    lrelu(bn_x(conv_xyz(y))) over y = cat[pc_i, pc_j - pc_i], both gathered through the one kNN graph of x; s = softmax over the k ranks
+    of conv_all(w0) (or conv_all's output itself with softmax=False).  Three per-point GEMMs (PQ_h [M,2Fin], PQ_f [M,32] from x, PQ_x
+    [M,32] from pc); of the two 16-wide branches only their product w0 [M*k,16] is stored (edge_weight.edge_weight_gather2) and the
+    backward recomputes a_f and a_x from PQ_f, PQ_x and the graph (edge_weight_split).  z2 [M*k,64] and z3 [M*k,Fin] (the one edge-sized
+    tensor of the forward) are stored as in the weighted layer; the backward holds du and g3 / dz3 beside it.
+    holder: softmax, slope, bns = the six nn.BatchNorm2d modules (h, f, x, 2, 3, c); parameters of inte_conv_hk, conv_fea, conv_xyz,
+    conv_all.0/1, conv_all.3/4 and conv2.  Differentiable in x, pc and every parameter."""
+
+    @staticmethod
+    def forward(ctx, h, x, pc, *params):
+        Wh, bh, gh, beh, Wf, bf, gf, bef, Wx, bx, gx, bex, Wa2, ba2, g2, be2, Wa3, ba3, g3, be3, W2, b2, gc, bec = params
+        B, Fin, N = x.shape
+        k, M, train = h.k, B * N, h.training
+        E = M * k
+        x_pm, pc_pm = ops.cm_to_pm(x), ops.cm_to_pm(pc)
+        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
+        Wst_h, Wst_f, Wst_x, _, _, Wm2, _, Wm3, _, W2i, _ = coord_images(Wh, Wf, Wx, Wa2, Wa3, W2)
+        # exact=True: fp32 operands whatever ops.set_mfma_operands selected
+        PQh = ops.gemm_nt(x_pm, Wst_h, pq_bias(bh), exact=True)
+        PQf = ops.gemm_nt(x_pm, Wst_f, pq_bias(bf), exact=True)
+        PQx = ops.gemm_nt(pc_pm, Wst_x, pq_bias(bx), exact=True)
+        sth = bn_stats(h.bns[0], train, E, gh, beh, records=edge_records(PQh, idx) if train else None)
+        stf = bn_stats(h.bns[1], train, E, gf, bef, records=edge_records(PQf, idx) if train else None)
+        stx = bn_stats(h.bns[2], train, E, gx, bex, records=edge_records(PQx, idx) if train else None)
+        w0 = edge_weight.edge_weight_gather2(PQf, PQx, idx, stf[0], stf[1], stx[0], stx[1], h.slope)
+        # w0 is activated already: conv_all.0 reads it without a prologue
+        if train:
+            z2, m, v = ops.gemm_nt(w0, Wm2, ba2, stats=True, exact=True)
+            st2 = bn_stats(h.bns[3], True, E, g2, be2, moments=(m, v))
+            z3, m, v = ops.gemm_nt(z2, Wm3, ba3, pro=(st2[0], st2[1], h.slope), stats=True, exact=True)
+            st3 = bn_stats(h.bns[4], True, E, g3, be3, moments=(m, v))
+        else:
+            st2 = bn_stats(h.bns[3], False, E, g2, be2)
+            z2 = ops.gemm_nt(w0, Wm2, ba2, exact=True)
+            st3 = bn_stats(h.bns[4], False, E, g3, be3)
+            z3 = ops.gemm_nt(z2, Wm3, ba3, pro=(st2[0], st2[1], h.slope), exact=True)
+        norm = edge_weight.edge_weight_norm(z3, k, st3[0], st3[1], h.slope) if h.softmax else None
+        Y, rec = split_records(edge_weight.edge_weight_gemm(PQh, idx, sth[0], sth[1], z3, st3[0], st3[1], norm, W2i, b2, stats=train, slope=h.slope),
+                               train)
+        stc = bn_stats(h.bns[5], train, M, gc, bec, records=rec)
+        del rec
+        out_pm = ops.affine_act(Y, stc[0], stc[1], h.slope)
+        h.last_idx = idx
+        ctx.h, ctx.st, ctx.norm = h, (sth, stf, stx, st2, st3, stc), norm
+        ctx.save_for_backward(x, pc, PQh, PQf, PQx, w0, z2, z3, Y, idx, Wh, Wf, Wx, Wa2, Wa3, W2, g2, g3, gc)
+        return ops.pm_to_cm(out_pm, B, N)
+
+    @staticmethod
+    def backward(ctx, dout):
+        refuse_double_backward("deform_edgeConv")
+        return CoordRankEdgeConvFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        x, pc, PQh, PQf, PQx, w0, z2, z3, Y, idx, Wh, Wf, Wx, Wa2, Wa3, W2, g2, g3, gc = ctx.saved_tensors
+        h = ctx.h
+        B, Fin, N = x.shape
+        k, M, train = h.k, B * N, h.training
+        E = M * k
+        Fout, F1, Fm = W2.shape[0], Wf.shape[0], Wa2.shape[0]
+        sth, stf, stx, (sc2, sh2, inv2, mu2), (sc3, sh3, inv3, mu3), stc = ctx.st
+        sch, shh, invh, muh = sth
+        need = ctx.needs_input_grad
+        _, _, _, Wall_t, Wst_xt, _, Wm2t, _, Wm3t, _, W2t = coord_images(Wh, Wf, Wx, Wa2, Wa3, W2)
+        dy, sumsc = lrelu_bn_bwd(dout, Y, stc, gc, h, h.slope)
+        # the product h*s, both LeakyReLUs and the softmax: du and g3 [M,k,Fin] are the two per-edge buffers of the backward
+        du, sumsh, gz3, sums3 = edge_weight.edge_weight_dgrad(dy, W2t, PQh, idx, sch, shh, muh, invh, z3, sc3, sh3, mu3, inv3, ctx.norm, h.slope)
+        rowptr, src = ops.csr_build(idx, B, N)
+        dPQh = rank_scatter(du, rowptr, src, sth, PQh, idx, sumsh, train)
+        del du
+        # the weight MLP, last layer first
+        dz3 = ops.bn_bwd_apply(gz3, z3, mu3, inv3, g3, used(sums3, train), E)
+        del gz3
+        dWa3 = ops.gemm_tn(dz3, z2, pro=(sc2, sh2, h.slope), exact=True).view(Fin, Fm, 1, 1) if need[19] else None
+        dba3 = dbias(dz3, train) if need[20] else None
+        gz2, t1, t2 = ops.gemm_nt_bnbwd(dz3, Wm3t, z2, sc2, sh2, mu2, inv2, h.slope, exact=True)
+        del dz3
+        sums2 = torch.cat([t1, t2])
+        dz2 = ops.bn_bwd_apply(gz2, z2, mu2, inv2, g2, used(sums2, train), E)
+        del gz2
+        dWa2 = ops.gemm_tn(dz2, w0, exact=True).view(Fm, F1, 1, 1) if need[15] else None
+        dba2 = dbias(dz2, train) if need[16] else None
+        # no BatchNorm between w0 and conv_all.0: a plain product, then the two branches' LeakyReLU'd BatchNorms
+        dw0 = ops.gemm_nt(dz2, Wm2t, exact=True)
+        del dz2
+        gf_, sumsf, gx_, sumsx = edge_weight.edge_weight_split(dw0, PQf, PQx, idx, stf[0], stf[1], stf[3], stf[2], stx[0], stx[1], stx[3], stx[2],
+                                                               h.slope)
+        del dw0
+        dPQf = rank_scatter(gf_, rowptr, src, stf, PQf, idx, sumsf, train)
+        del gf_
+        dPQx = rank_scatter(gx_, rowptr, src, stx, PQx, idx, sumsx, train)
+        del gx_
+        dW2 = None
+        if need[23]:                                                     # after du and g3 have died: its split workspace is not held beside them
+            dW2 = edge_weight.edge_weight_wgrad(PQh, idx, sch, shh, z3, sc3, sh3, ctx.norm, dy, h.slope)
+            dW2 = dW2.view(Fout, k, Fin).permute(0, 2, 1).unsqueeze(2).contiguous()
+        dPQ = torch.cat([dPQh, dPQf], dim=1)                             # [M, 2Fin + 32]: both feature-side branches feed one product pair
+        dWh = dWf = dWx = None
+        if need[3] or need[7]:
+            dWst = ops.gemm_tn(dPQ, ops.cm_to_pm(x), exact=True)         # rows of dW'_P, then of dW'_Q, per branch
+            dWh, dWf = unstacked_grad(dWst[:2 * Fin]), unstacked_grad(dWst[2 * Fin:])
+        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wall_t, exact=True), B, N) if need[1] else None
+        if need[11]:
+            dWx = unstacked_grad(ops.gemm_tn(dPQx, ops.cm_to_pm(pc), exact=True))
+        dpc = ops.pm_to_cm(ops.gemm_nt(dPQx, Wst_xt, exact=True), B, N) if need[2] else None
+        dbh = dbias(dPQh[:, Fin:], train) if need[4] else None
+        dbf = dbias(dPQf[:, F1:], train) if need[8] else None
+        dbx = dbias(dPQx[:, F1:], train) if need[12] else None
+        db2 = dbias(dy, train) if need[24] else None
+        return (None, dx, dpc, dWh, dbh) + gb(sumsh, need, 5) + (dWf, dbf) + gb(sumsf, need, 9) + (dWx, dbx) + gb(sumsx, need, 13) + \
+            (dWa2, dba2) + gb(sums2, need, 17) + (dWa3, dba3) + gb(sums3, need, 21) + (dW2, db2) + gb(sumsc, need, 25)

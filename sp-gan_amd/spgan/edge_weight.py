@@ -1,5 +1,6 @@
 """Tensor-level wrappers of the weighted full-rank edge convolution's launchers (csrc/edge_rank.hip; include/spgan_hip.h): the passes behind
-`spgan.deform_edgeConv_feat` (edge_conv.WeightedRankEdgeConvFn).  PQ, idx, scale1 / shift1 and W2i as in spgan.edge_rank; the per-edge weight
+`spgan.deform_edgeConv_feat` (edge_conv.WeightedRankEdgeConvFn) and, with the two-branch passes at the end, `spgan.deform_edgeConv`
+(edge_conv.CoordRankEdgeConvFn).  PQ, idx, scale1 / shift1 and W2i as in spgan.edge_rank; the per-edge weight
 s(i,r,c) is the softmax over the k ranks of a3 = lrelu(scale3*z3 + shift3) with z3 [M*k, F1] the stored pre-norm output of the weight MLP
 and norm = (wmax, wrs) [M,F1] x 2 its per-(point, channel) normaliser (edge_weight_norm); norm=None: s = a3 (softmax=False).
 h, s and h*s exist only inside the kernels.  Exact fp32 MFMA products, as spgan.edge_rank."""
@@ -12,7 +13,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .edge_max import tile_sums
-from .edge_rank import K_MAX, SLOPE, Norm, _dgrad_sizes, _graph, _mod, edge_rank_gemm, edge_rank_wgrad
+from .edge_rank import K_MAX, SLOPE, Norm, _dgrad_sizes, _graph, _mod, edge_rank_gemm, edge_rank_wgrad, tile_points
 from .ops import _f32, _ld, _p, _s, _vec
 
 Tensor = torch.Tensor
@@ -65,3 +66,43 @@ def edge_weight_dgrad(dy: Tensor, W2t: Tensor, PQ: Tensor, idx: Tensor, scale1: 
                                               float(slope), md[0], md[1], md[2], _p(_vec(mean3, F1, "mean3")), _p(_vec(invstd3, F1, "invstd3")),
                                               md[3], md[4], _p(du), _p(g3), _p(part[0]), _p(part[1]), _s()), "edge_weight_dgrad", M=M_, k=k, F1=F1, O=O)
     return du, tile_sums(part[0], M_, tp), g3, tile_sums(part[1], M_, tp)
+
+
+def _graph2(PQa: Tensor, PQb: Tensor, idx: Tensor):
+    M_, k, F_ = _graph(PQa, idx)
+    if _graph(PQb, idx) != (M_, k, F_):
+        raise ValueError("PQa and PQb must both be [M, 2*F] = [%d, %d], got %s and %s" % (M_, 2 * F_, tuple(PQa.shape), tuple(PQb.shape)))
+    return M_, k, F_
+
+
+def edge_weight_gather2(PQa: Tensor, PQb: Tensor, idx: Tensor, scale_a: Tensor, shift_a: Tensor, scale_b: Tensor, shift_b: Tensor,
+                        slope: float = SLOPE) -> Tensor:
+    """w0 [M*k, F] = a_a * a_b, a_x = lrelu(scale_x * (Qx_i + Px_idx[i,r]) + shift_x), row i*k + r: the product of two activated narrow edge
+    branches over one graph (deform_edgeConv's feature and coordinate branch, F = 16); neither branch is stored."""
+    M_, k, F_ = _graph2(PQa, PQb, idx)
+    w0 = torch.empty((M_ * k, F_), dtype=torch.float32, device=PQa.device)
+    check(_lib.load().spgan_edge_weight_gather2(_p(PQa), 2 * F_, _p(PQb), 2 * F_, _p(idx), M_, k, F_, _p(_vec(scale_a, F_, "scale_a")),
+                                                _p(_vec(shift_a, F_, "shift_a")), _p(_vec(scale_b, F_, "scale_b")), _p(_vec(shift_b, F_, "shift_b")),
+                                                float(slope), _p(w0), _s()), "edge_weight_gather2", M=M_, k=k, F=F_)
+    return w0
+
+
+def edge_weight_split(dw0: Tensor, PQa: Tensor, PQb: Tensor, idx: Tensor, scale_a: Tensor, shift_a: Tensor, mean_a: Tensor, invstd_a: Tensor,
+                      scale_b: Tensor, shift_b: Tensor, mean_b: Tensor, invstd_b: Tensor, slope: float = SLOPE):
+    """dw0 [M*k, F], the gradient of edge_weight_gather2's product -> (ga [M,k,F] = lrelu'(pre_a) * dw0 * a_b, sums_a [2F] = [sum ga |
+    sum ga*zhat_a], gb [M,k,F] = lrelu'(pre_b) * dw0 * a_a, sums_b [2F]): the gradients reaching the two branches' BatchNorm outputs, in
+    the form edge_rank.edge_rank_scatter takes."""
+    M_, k, F_ = _graph2(PQa, PQb, idx)
+    _f32(dw0, "dw0")
+    if not dw0.is_contiguous() or dw0.numel() != M_ * k * F_:
+        raise ValueError("dw0 must be contiguous [M*k, F] = [%d, %d], got %s" % (M_ * k, F_, tuple(dw0.shape)))
+    tp = tile_points(k)
+    ga = torch.empty((M_, k, F_), dtype=torch.float32, device=PQa.device)
+    gb = torch.empty_like(ga)
+    part = torch.empty((2, (M_ + tp - 1) // tp, F_, 2), dtype=torch.float32, device=PQa.device)
+    v = lambda t, n: _p(_vec(t, F_, n))
+    check(_lib.load().spgan_edge_weight_split(_p(dw0), _p(PQa), 2 * F_, _p(PQb), 2 * F_, _p(idx), M_, k, F_, v(scale_a, "scale_a"), v(shift_a, "shift_a"),
+                                              v(mean_a, "mean_a"), v(invstd_a, "invstd_a"), v(scale_b, "scale_b"), v(shift_b, "shift_b"),
+                                              v(mean_b, "mean_b"), v(invstd_b, "invstd_b"), float(slope), _p(ga), _p(gb), _p(part[0]), _p(part[1]),
+                                              _s()), "edge_weight_split", M=M_, k=k, F=F_)
+    return ga, tile_sums(part[0], M_, tp), gb, tile_sums(part[1], M_, tp)

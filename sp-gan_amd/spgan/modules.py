@@ -854,3 +854,79 @@ class deform_edgeConv_feat(nn.Module):
         out = edge_conv.WeightedRankEdgeConvFn.apply(h, x.contiguous(), *params)
         self.last_idx = h.last_idx
         return out
+
+
+class deform_edgeConv(nn.Module):
+    """Generation/modules.py:1468-1540: [B,Fin,N] x [B,3,N] -> [B,Fout,N], the coordinate-guided full-rank edge convolution:
+    conv2(inte_conv_hk(e) * w) with (e, y) = get_edge_features_xyz(x, pc), w = conv_all(conv_fea(e) * conv_xyz(y)) -- conv_fea 2Fin -> 16,
+    conv_xyz 6 -> 16, conv_all 16 -> 64 -> Fin, each Conv2d 1x1 + BatchNorm2d + LeakyReLU -- normalised by a softmax over the k neighbours
+    (softmax=True), and conv2 = Conv2d(Fin -> Fout, [1,k]) + BatchNorm2d + LeakyReLU.  Evaluated by edge_conv.CoordRankEdgeConvFn
+    (csrc/edge_rank.hip): neither edge tensor, the two 16-channel branches, the activated tensor, the weight nor their product exist in
+    memory; the forward keeps one [B*N,k,Fin] tensor, the backward two more.
+    As in the reference, conv2 is a plain nn.Sequential (keys conv2.0 / conv2.1) whose BatchNorm2d has Fin channels over the Fout channels
+    of its convolution: the constructor accepts any pair, so that reference state_dicts load strictly both ways, and the layer runs only
+    with Fin == Fout (forward raises ValueError otherwise, where the reference raises from batch_norm).
+    idx (an extension, as edgeConv's): the graph to use instead of the kNN graph of x, int64 [B, N*k] local indices (range-checked outside
+    a capture) or int32 [B*N,k] global rows (trusted).  1 <= k <= 32.  Once differentiable in x, pc and the parameters.  last_idx: the
+    graph of the latest forward."""
+
+    def __init__(self, Fin, Fout, k, softmax=True):
+        super().__init__()
+        if not 1 <= k <= 32:
+            raise ValueError("deform_edgeConv: k must lie in 1..32, got k=%d (Fin=%d, Fout=%d)" % (k, Fin, Fout))
+        if Fin < 1 or Fout < 1:
+            raise ValueError("deform_edgeConv: Fin and Fout must be positive, got Fin=%d, Fout=%d" % (Fin, Fout))
+        self.k = k
+        self.Fin = Fin
+        self.Fout = Fout
+        self.softmax = softmax
+        self.conv2 = nn.Sequential(
+            nn.Conv2d(Fin, Fout, [1, k], [1, 1]),
+            nn.BatchNorm2d(Fin),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.conv_xyz = nn.Sequential(
+            nn.Conv2d(6, 16, 1),
+            nn.BatchNorm2d(16),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.conv_fea = nn.Sequential(
+            nn.Conv2d(2 * Fin, 16, 1),
+            nn.BatchNorm2d(16),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.conv_all = nn.Sequential(
+            nn.Conv2d(16, 64, 1),
+            nn.BatchNorm2d(64),
+            nn.LeakyReLU(inplace=True),
+            nn.Conv2d(64, Fin, 1),
+            nn.BatchNorm2d(Fin),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.inte_conv_hk = nn.Sequential(
+            nn.Conv2d(2 * Fin, Fin, [1, 1], [1, 1]),
+            nn.BatchNorm2d(Fin),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.last_idx: Optional[torch.Tensor] = None
+
+    def forward(self, x, pc, idx: Optional[torch.Tensor] = None):
+        name = "deform_edgeConv"
+        if self.Fin != self.Fout:
+            raise ValueError("%s: conv2's BatchNorm2d has Fin=%d channels over the Fout=%d channels of its convolution: the layer runs only "
+                             "with Fin == Fout" % (name, self.Fin, self.Fout))
+        layers = [(self.inte_conv_hk[0], self.inte_conv_hk[1]), (self.conv_fea[0], self.conv_fea[1]), (self.conv_xyz[0], self.conv_xyz[1]),
+                  (self.conv_all[0], self.conv_all[1]), (self.conv_all[3], self.conv_all[4]), (self.conv2[0], self.conv2[1])]
+        slopes = {float(a.negative_slope) for a in (self.inte_conv_hk[2], self.conv_fea[2], self.conv_xyz[2], self.conv_all[2], self.conv_all[5],
+                                                    self.conv2[2])}
+        B, N, idx, knn_mode = check_edge_input(name, x, idx, self.k, self.Fin, self.Fout, [bn for _, bn in layers],
+                                               None if len(slopes) == 1 else "the six LeakyReLUs must share one slope, got %s" % sorted(slopes))
+        _require_gpu(pc, name + " pc")
+        if pc.dim() != 3 or pc.shape[0] != B or pc.shape[1] != 3 or pc.shape[2] != N:
+            raise ValueError("%s: pc must be [B,3,N] for x [B,C,N], got %s and %s" % (name, tuple(pc.shape), tuple(x.shape)))
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, softmax=bool(self.softmax), idx=idx, knn_mode=knn_mode,
+                    slope=slopes.pop(), bns=tuple(bn for _, bn in layers), last_idx=None)
+        params = [t for conv, bn in layers for t in (conv.weight, conv.bias, bn.weight, bn.bias)]
+        out = edge_conv.CoordRankEdgeConvFn.apply(h, x.contiguous(), pc.contiguous(), *params)
+        self.last_idx = h.last_idx
+        return out
