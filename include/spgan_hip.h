@@ -796,6 +796,27 @@ int spgan_edge_weight_split(const float* dW0, const float* PQa, int lda, const f
                             const float* scale_a, const float* shift_a, const float* mean_a, const float* invstd_a, const float* scale_b,
                             const float* shift_b, const float* mean_b, const float* invstd_b, float slope, float* GA, float* GB, float* partials_a,
                             float* partials_b, spgan_stream_t s);
+/* Bilateral upsampling edge convolution (csrc/edge_rank.hip): the core of bilateral_upsample_edgeConv (Generation/modules.py:847-925).  The
+ * weighted product above with h read from a stored tensor instead of gathered rows: U [M,k,F1] contiguous holds the pre-norm value of
+ * (point i, rank r, channel c) and the BatchNorm affine alternates with the rank's parity,
+ *   h(i,r,c) = lrelu(scale1[(r&1)*F1 + c] * U[i,r,c] + shift1[(r&1)*F1 + c], slope)      (scale1, shift1, mean1, invstd1: [2*F1]);
+ * z3, scale3, shift3, wmax, wrs and s as in the weighted layer.  k even, 2 <= k <= 28, any M, F1, O; rows of F1 % 4 == 0 floats on 16-byte
+ * aligned operands are staged as 16-byte pieces, everything else by scalars.
+ *   spgan_edge_stored_gemm:   spgan_edge_weight_gemm over the stored h (same tiling, partials and finalize; b2 and partials may be NULL).
+ *   spgan_edge_stored_wgrad:  spgan_edge_weight_wgrad over the stored h (workspace: spgan_edge_rank_wgrad_ws_bytes).
+ *   spgan_edge_stored_dgrad:  spgan_edge_weight_dgrad over the stored h: dU[i,r,c] = lrelu'(a_h) * dm * s with uhat = (U - mean1) * invstd1 and
+ *                             partials_u [ceil(M / tile_points)][2*F1][2], one column per (rank parity, channel); G3 and partials_3 as there.
+ *                             dU, G3 and U are distinct.  No float atomics: results repeat bit for bit. */
+int spgan_edge_stored_gemm(const float* U, int M, int k, int F1, const float* scale1, const float* shift1, float slope, const float* z3,
+                           const float* scale3, const float* shift3, const float* wmax, const float* wrs, const float* W2i, int ldw, const float* b2,
+                           int O, float* Y, int ldy, float* partials, spgan_stream_t s);
+int spgan_edge_stored_wgrad(const float* U, int M, int k, int F1, const float* scale1, const float* shift1, float slope, const float* z3,
+                            const float* scale3, const float* shift3, const float* wmax, const float* wrs, const float* dY, int ldg, int O,
+                            float* dW2i, int lddw, float* ws, size_t ws_bytes, spgan_stream_t s);
+int spgan_edge_stored_dgrad(const float* dY, int ldg, const float* W2t, int ldwt, const float* U, int M, int k, int F1, int O, const float* scale1,
+                            const float* shift1, const float* mean1, const float* invstd1, float slope, const float* z3, const float* scale3,
+                            const float* shift3, const float* mean3, const float* invstd3, const float* wmax, const float* wrs, float* dU,
+                            float* G3, float* partials_u, float* partials_3, spgan_stream_t s);
 /* Per-channel scalar algebra of the double backward, one launch each:
  *   coeffs out4C = [dgammaA | sbarA | xsum0 | xsum1];  phaseb: sums2C = [xsum0+gamma*s0 | xsum1+gamma*s1+invstd*sbarA], dgamma = dgammaA+s1 */
 int spgan_bn_dbl_coeffs(const float* U0, const float* U1, const float* Ugz, const float* S0, const float* S1, const float* gamma,

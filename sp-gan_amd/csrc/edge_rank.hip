@@ -32,6 +32,11 @@
 //                              (sum G, sum G * zhat) of each branch, as spgan_edge_rank_dgrad writes them
 // Both are gather passes over rows of F floats: consecutive lanes take consecutive 16-byte pieces of consecutive edge rows.
 //
+// The bilateral upsampling layer (bilateral_upsample_edgeConv, Generation/modules.py:847-925) multiplies the stored pre-norm tensor of
+// upsample_edgeConv's interpolation, U [M,k,F1] with rows (point, rank) and a BatchNorm affine that alternates with the rank's parity, by the
+// same per-edge weight.  spgan_edge_stored_gemm / _wgrad / _dgrad are spgan_edge_weight_gemm / _wgrad / _dgrad with h read from U
+// (stored_h4) instead of gathered through the graph; s comes from weight_s() as everywhere.
+//
 // MFMA operand order as in edge_window.hip: a 16-wide K block is one 16-byte fragment per lane (lane group g = lane>>4 holds K elements
 // 4g..4g+3), consumed by four MFMA steps; A and B agree on that order.  fp32 operands, fp32 accumulation: exact products.
 #include "common.hpp"
@@ -96,6 +101,19 @@ __device__ __forceinline__ f32x4 rank_h4(const float* __restrict__ PQ, int ld, i
   return h;
 }
 
+// The stored form of h (bilateral_upsample_edgeConv): U [M,k,F1] holds the pre-norm value of (point i, rank r, channel c) itself and the
+// BatchNorm affine alternates with the rank's parity: sc, sh [2*F1], entry (r & 1) * F1 + c.  No graph: the row is (i*k + r).
+template <bool VEC>
+__device__ __forceinline__ f32x4 stored_h4(const float* __restrict__ U, int F1, int k, int i, int r, int c, const float* __restrict__ sc,
+                                           const float* __restrict__ sh, float slope) {
+  const int nv = F1 - c, ch = (r & 1) * F1 + c;
+  const f32x4 u = ld4<VEC>(U + ((size_t)i * k + r) * F1 + c, nv), a = ld4<VEC>(sc + ch, nv), s = ld4<VEC>(sh + ch, nv);
+  f32x4 h;
+#pragma unroll
+  for (int v = 0; v < 4; ++v) h[v] = lrelu_f(fmaf(a[v], u[v], s[v]), slope);
+  return h;
+}
+
 // The per-edge weight of the weighted layers (deform_edgeConv_feat): s(i,r,c) = softmax over r of a3 = lrelu(sc3 * z3 + sh3) with
 // z3 [M,k,F1] the stored pre-norm output of the weight MLP, evaluated from the per-(point, channel) normaliser wmax = max_r a3 and
 // wrs = 1 / sum_r exp(a3 - wmax) (spgan_edge_weight_norm); wmax == nullptr: s = a3 (softmax=False).  Every kernel forms s with
@@ -124,7 +142,8 @@ __device__ __forceinline__ f32x4 weight_s4(const WMod& m, int F1, int k, int i, 
 // Per wave: 2 blocks of 16 points x (2 groups of 128 columns) x 2 blocks of 16 output columns; the four waves of a workgroup take 128
 // consecutive output columns of each group, so one staging serves 256 output columns.
 // MOD: the staged operand is h * s (WMod above): spgan_edge_weight_gemm.
-template <bool VEC, bool MOD>
+// STORED: h comes from the stored rows PQ = U [M,k,F1] (stored_h4; ld and idx are not read): spgan_edge_stored_gemm.
+template <bool VEC, bool MOD, bool STORED = false>
 __global__ __launch_bounds__(256, 2) void edge_rank_gemm_kernel(const float* __restrict__ PQ, int ld, const int32_t* __restrict__ idx, int M, int k,
                                                                 int F1, const float* __restrict__ sc, const float* __restrict__ sh, float slope,
                                                                 const float* __restrict__ W, int ldw, const float* __restrict__ b2, int O,
@@ -154,7 +173,8 @@ __global__ __launch_bounds__(256, 2) void edge_rank_gemm_kernel(const float* __r
           f32x4 v = {0.f, 0.f, 0.f, 0.f};
           if (p < np && c0 + cc < F1) {
             const int i = p0 + p;
-            v = rank_h4<VEC>(PQ, ld, F1, i, neighbour(idx, i, k, r0 + rs, M), c0 + cc, sc, sh, slope);
+            if constexpr (STORED) v = stored_h4<VEC>(PQ, F1, k, i, r0 + rs, c0 + cc, sc, sh, slope);
+            else v = rank_h4<VEC>(PQ, ld, F1, i, neighbour(idx, i, k, r0 + rs, M), c0 + cc, sc, sh, slope);
             if constexpr (MOD) v *= weight_s4<VEC>(md, F1, k, i, r0 + rs, c0 + cc, slope);
           }
           *reinterpret_cast<f32x4*>(sm + (rs * ER_PT + p) * ER_PST + cc) = v;
@@ -324,7 +344,7 @@ inline RwPlan er_wg_plan(int M, int k, int F1, int O) {
   return p;
 }
 
-template <bool VEC, bool MOD>
+template <bool VEC, bool MOD, bool STORED = false>
 __global__ __launch_bounds__(256) void edge_rank_wgrad_kernel(const float* __restrict__ PQ, int ld, const int32_t* __restrict__ idx, int M, int k, int F1,
                                                               const float* __restrict__ sc, const float* __restrict__ sh, float slope,
                                                               const float* __restrict__ G, int ldg, int O, float* __restrict__ ws, RwPlan pl, WMod md) {
@@ -349,7 +369,8 @@ __global__ __launch_bounds__(256) void edge_rank_wgrad_kernel(const float* __res
       const int i = pb + p;
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (i < end && r0 + rb < k && c0 + cc < F1) {
-        v = rank_h4<VEC>(PQ, ld, F1, i, neighbour(idx, i, k, r0 + rb, M), c0 + cc, sc, sh, slope);
+        if constexpr (STORED) v = stored_h4<VEC>(PQ, F1, k, i, r0 + rb, c0 + cc, sc, sh, slope);
+        else v = rank_h4<VEC>(PQ, ld, F1, i, neighbour(idx, i, k, r0 + rb, M), c0 + cc, sc, sh, slope);
         if constexpr (MOD) v *= weight_s4<VEC>(md, F1, k, i, r0 + rb, c0 + cc, slope);
       }
       *reinterpret_cast<f32x4*>(sm + (p * ER_RB + rb) * ER_WPST + cc) = v;
@@ -624,6 +645,140 @@ __global__ __launch_bounds__(256) void edge_weight_dgrad_kernel(const float* __r
   }
 }
 
+// edge_weight_dgrad_kernel for the stored form of h (stored_h4): no graph, a1 = sc[(r & 1)*F1 + c] * U + sh[..], and the h branch's
+// records have one column per (rank parity, channel): partU [tiles][2*F1][2].  k is even, so the rank loop runs over pairs and every
+// per-parity value stays in a register.  dU receives dm in pass 0 and gU in pass 1: it must not be U.
+template <bool VEC>
+__global__ __launch_bounds__(256) void edge_stored_dgrad_kernel(const float* __restrict__ G, int ldg, const float* __restrict__ Wt, int ldwt,
+                                                                const float* __restrict__ U, int M, int k, int F1, int O,
+                                                                const float* __restrict__ sc, const float* __restrict__ sh,
+                                                                const float* __restrict__ mean, const float* __restrict__ invstd, float slope,
+                                                                WMod md, const float* __restrict__ mean3, const float* __restrict__ invstd3,
+                                                                float* __restrict__ dU, float* __restrict__ G3, float* __restrict__ partU,
+                                                                float* __restrict__ part3) {
+  const int bx = xcd_block();
+  const int p0 = bx * ER_PT;
+  if (p0 >= M) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, g = lane >> 4;
+  const bool soft = md.wmax != nullptr;
+  const int npass = soft ? 2 : 1;
+  for (int cp = 0; cp < F1; cp += 128) {
+    const int cw = cp + wave * 32;
+    if (cw >= F1) continue;
+    float a_[2][2], s_[2][2], mu[2][2], is[2][2], a3_[2], s3_[2], mu3[2], is3[2];
+    float u1[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, u2[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, w1[2] = {0.f, 0.f}, w2[2] = {0.f, 0.f};
+    float t[2][4][2], mx[2][4][2], rs[2][4][2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+      const int c = cw + cb * 16 + col;
+      const bool ok = c < F1;
+#pragma unroll
+      for (int hp = 0; hp < 2; ++hp) {
+        const int ch = hp * F1 + c;
+        a_[hp][cb] = ok ? sc[ch] : 0.f; s_[hp][cb] = ok ? sh[ch] : 0.f; mu[hp][cb] = ok ? mean[ch] : 0.f; is[hp][cb] = ok ? invstd[ch] : 0.f;
+      }
+      a3_[cb] = ok ? md.sc3[c] : 0.f; s3_[cb] = ok ? md.sh3[c] : 0.f; mu3[cb] = ok ? mean3[c] : 0.f; is3[cb] = ok ? invstd3[c] : 0.f;
+#pragma unroll
+      for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int p = p0 + pb * 16 + 4 * g + v;
+          const bool on = soft && ok && p < M;
+          t[pb][v][cb] = 0.f;
+          mx[pb][v][cb] = on ? md.wmax[(size_t)p * F1 + c] : 0.f;
+          rs[pb][v][cb] = on ? md.wrs[(size_t)p * F1 + c] : 0.f;
+        }
+    }
+    for (int pass = 0; pass < npass; ++pass) {
+      const bool last = pass == npass - 1;
+      for (int r2 = 0; r2 < k; r2 += 2) {
+#pragma unroll
+        for (int hp = 0; hp < 2; ++hp) {
+          const int r = r2 + hp;
+          f32x4 acc[2][2];
+          acc[0][0] = acc[0][1] = acc[1][0] = acc[1][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (pass == 0) {
+            for (int ob = 0; ob < O; ob += 16) {
+              const int o = ob + 4 * g;
+              f32x4 a[2], b[2];
+#pragma unroll
+              for (int pb = 0; pb < 2; ++pb) {
+                const int p = p0 + pb * 16 + col;
+                a[pb] = ld4<VEC>(G + (size_t)min(p, M - 1) * ldg + o, p < M ? O - o : 0);
+              }
+#pragma unroll
+              for (int cb = 0; cb < 2; ++cb) {
+                const int c = cw + cb * 16 + col;
+                b[cb] = ld4<VEC>(Wt + ((size_t)r * F1 + min(c, F1 - 1)) * ldwt + o, c < F1 ? O - o : 0);
+              }
+#pragma unroll
+              for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) acc[pb][cb] = mfma4(a[pb], b[cb], acc[pb][cb]);
+            }
+          }
+#pragma unroll
+          for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+              const int p = p0 + pb * 16 + 4 * g + v;
+              if (p >= M) continue;
+#pragma unroll
+              for (int cb = 0; cb < 2; ++cb) {
+                const int c = cw + cb * 16 + col;
+                if (c < F1) {
+                  const size_t e = ((size_t)p * k + r) * F1 + c;
+                  const float dm = pass == 0 ? acc[pb][cb][v] : dU[e];
+                  const float u = U[e];
+                  const float ah = fmaf(a_[hp][cb], u, s_[hp][cb]);
+                  const float z = md.z3[e];
+                  const float a3 = fmaf(a3_[cb], z, s3_[cb]);
+                  const float s = weight_s(lrelu_f(a3, slope), mx[pb][v][cb], rs[pb][v][cb], soft);
+                  const float ds = dm * lrelu_f(ah, slope);
+                  if (!last) {
+                    dU[e] = dm;
+                    t[pb][v][cb] = fmaf(ds, s, t[pb][v][cb]);
+                  } else {
+                    const float du = lrelu_mask(ah, slope) * dm * s;
+                    const float g3 = lrelu_mask(a3, slope) * (soft ? s * (ds - t[pb][v][cb]) : ds);
+                    dU[e] = du;
+                    G3[e] = g3;
+                    u1[hp][cb] += du;
+                    u2[hp][cb] = fmaf(du, (u - mu[hp][cb]) * is[hp][cb], u2[hp][cb]);
+                    w1[cb] += g3;
+                    w2[cb] = fmaf(g3, (z - mu3[cb]) * is3[cb], w2[cb]);
+                  }
+                }
+              }
+            }
+        }
+      }
+    }
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+      float c3 = w1[cb], d3 = w2[cb];
+      c3 += __shfl_xor(c3, 16); d3 += __shfl_xor(d3, 16);      // the four point groups, in a fixed order
+      c3 += __shfl_xor(c3, 32); d3 += __shfl_xor(d3, 32);
+      const int c = cw + cb * 16 + col;
+      if (g == 0 && c < F1) {
+        float* r3 = part3 + ((size_t)bx * F1 + c) * 2;
+        r3[0] = c3; r3[1] = d3;
+      }
+#pragma unroll
+      for (int hp = 0; hp < 2; ++hp) {
+        float a = u1[hp][cb], b = u2[hp][cb];
+        a += __shfl_xor(a, 16); b += __shfl_xor(b, 16);
+        a += __shfl_xor(a, 32); b += __shfl_xor(b, 32);
+        if (g == 0 && c < F1) {
+          float* ru = partU + ((size_t)bx * 2 * F1 + (size_t)hp * F1 + c) * 2;
+          ru[0] = a; ru[1] = b;
+        }
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------ the coordinate-guided layer's own passes
 // One activated branch value of deform_edgeConv's weight input: both kernels below form it here, so that the a the backward multiplies
 // with is the forward's, bit for bit.
@@ -740,13 +895,16 @@ inline bool mod_al16(const WMod& m) { return al16(m.z3) && al16(m.sc3) && al16(m
 
 // The [1,k] product and its weight gradient, plain (md == nullptr: spgan_edge_rank_*) or with the per-edge weight (spgan_edge_weight_*).
 int launch_gemm(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1, float slope,
-                const float* W2i, int ldw, const float* b2, int O, float* Y, int ldy, float* partials, const WMod* md, hipStream_t st) {
+                const float* W2i, int ldw, const float* b2, int O, float* Y, int ldy, float* partials, const WMod* md, hipStream_t st,
+                bool stored = false) {
   const bool vec = F1 % 4 == 0 && ld % 4 == 0 && ldw % 4 == 0 && al16(PQ) && al16(W2i) && al16(scale1) && al16(shift1) && (!md || mod_al16(*md));
   const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
   auto go = [&](auto kernel, const WMod& m) {
     hipLaunchKernelGGL(kernel, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, m);
   };
-  if (md && vec) go(edge_rank_gemm_kernel<true, true>, *md);
+  if (stored && vec) go(edge_rank_gemm_kernel<true, true, true>, *md);
+  else if (stored) go(edge_rank_gemm_kernel<false, true, true>, *md);
+  else if (md && vec) go(edge_rank_gemm_kernel<true, true>, *md);
   else if (md) go(edge_rank_gemm_kernel<false, true>, *md);
   else if (vec) go(edge_rank_gemm_kernel<true, false>, WMod{});
   else go(edge_rank_gemm_kernel<false, false>, WMod{});
@@ -754,14 +912,16 @@ int launch_gemm(const float* PQ, int ld, const int32_t* idx, int M, int k, int F
 }
 
 int launch_wgrad(const float* PQ, int ld, const int32_t* idx, int M, int k, int F1, const float* scale1, const float* shift1, float slope,
-                 const float* dY, int ldg, int O, float* dW2i, int lddw, float* ws, const WMod* md, hipStream_t st) {
+                 const float* dY, int ldg, int O, float* dW2i, int lddw, float* ws, const WMod* md, hipStream_t st, bool stored = false) {
   const RwPlan pl = er_wg_plan(M, k, F1, O);
   const bool vec = F1 % 4 == 0 && ld % 4 == 0 && al16(PQ) && al16(scale1) && al16(shift1) && (!md || mod_al16(*md));
   const dim3 gr(grid8((long)pl.tiles * pl.splits)), b(256);
   auto go = [&](auto kernel, const WMod& m) {
     hipLaunchKernelGGL(kernel, gr, b, 0, st, PQ, ld, idx, M, k, F1, scale1, shift1, slope, dY, ldg, O, ws, pl, m);
   };
-  if (md && vec) go(edge_rank_wgrad_kernel<true, true>, *md);
+  if (stored && vec) go(edge_rank_wgrad_kernel<true, true, true>, *md);
+  else if (stored) go(edge_rank_wgrad_kernel<false, true, true>, *md);
+  else if (md && vec) go(edge_rank_wgrad_kernel<true, true>, *md);
   else if (md) go(edge_rank_wgrad_kernel<false, true>, *md);
   else if (vec) go(edge_rank_wgrad_kernel<true, false>, WMod{});
   else go(edge_rank_wgrad_kernel<false, false>, WMod{});
@@ -915,5 +1075,50 @@ extern "C" int spgan_edge_weight_split(const float* dW0, const float* PQa, int l
   const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
   if (v4) hipLaunchKernelGGL(edge_weight_split_kernel<4>, gr, b, 0, (hipStream_t)s_, dW0, A, B, idx, M, k, F, slope, GA, GB, partials_a, partials_b);
   else hipLaunchKernelGGL(edge_weight_split_kernel<1>, gr, b, 0, (hipStream_t)s_, dW0, A, B, idx, M, k, F, slope, GA, GB, partials_a, partials_b);
+  return spgan_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------ the bilateral layer (bilateral_upsample_edgeConv)
+namespace {
+inline bool stored_ok(int M, int k, int F1, int O) { return sizes_ok(M, k, F1, O) && k >= 2 && k <= 28 && k % 2 == 0; }
+}  // namespace
+
+extern "C" int spgan_edge_stored_gemm(const float* U, int M, int k, int F1, const float* scale1, const float* shift1, float slope, const float* z3,
+                                      const float* scale3, const float* shift3, const float* wmax, const float* wrs, const float* W2i, int ldw,
+                                      const float* b2, int O, float* Y, int ldy, float* partials, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(U && scale1 && shift1 && W2i && Y && stored_ok(M, k, F1, O) && ldw >= k * F1 && ldy >= O);
+  SPGAN_CHECK_ARG(mod_ok(z3, scale3, shift3, wmax, wrs));
+  const WMod md{z3, scale3, shift3, wmax, wrs};
+  return launch_gemm(U, F1, nullptr, M, k, F1, scale1, shift1, slope, W2i, ldw, b2, O, Y, ldy, partials, &md, (hipStream_t)s_, true);
+}
+
+extern "C" int spgan_edge_stored_wgrad(const float* U, int M, int k, int F1, const float* scale1, const float* shift1, float slope, const float* z3,
+                                       const float* scale3, const float* shift3, const float* wmax, const float* wrs, const float* dY, int ldg,
+                                       int O, float* dW2i, int lddw, float* ws, size_t ws_bytes, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(U && scale1 && shift1 && dY && dW2i && ws && stored_ok(M, k, F1, O) && ldg >= O && lddw >= k * F1);
+  SPGAN_CHECK_ARG(mod_ok(z3, scale3, shift3, wmax, wrs) && ws_bytes >= spgan_edge_rank_wgrad_ws_bytes(M, k, F1, O));
+  const WMod md{z3, scale3, shift3, wmax, wrs};
+  return launch_wgrad(U, F1, nullptr, M, k, F1, scale1, shift1, slope, dY, ldg, O, dW2i, lddw, ws, &md, (hipStream_t)s_, true);
+}
+
+extern "C" int spgan_edge_stored_dgrad(const float* dY, int ldg, const float* W2t, int ldwt, const float* U, int M, int k, int F1, int O,
+                                       const float* scale1, const float* shift1, const float* mean1, const float* invstd1, float slope,
+                                       const float* z3, const float* scale3, const float* shift3, const float* mean3, const float* invstd3,
+                                       const float* wmax, const float* wrs, float* dU, float* G3, float* partials_u, float* partials_3,
+                                       spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(dY && W2t && U && scale1 && shift1 && mean1 && invstd1 && stored_ok(M, k, F1, O));
+  SPGAN_CHECK_ARG(mod_ok(z3, scale3, shift3, wmax, wrs) && mean3 && invstd3 && dU && G3 && dU != G3 && dU != U && G3 != U && partials_u && partials_3 &&
+                  partials_u != partials_3);
+  SPGAN_CHECK_ARG(ldg >= O && ldwt >= O);
+  const WMod md{z3, scale3, shift3, wmax, wrs};
+  const bool vec = O % 4 == 0 && ldg % 4 == 0 && ldwt % 4 == 0 && al16(dY) && al16(W2t);
+  const dim3 gr(grid8(cdiv(M, ER_PT))), b(256);
+  hipStream_t st = (hipStream_t)s_;
+  if (vec)
+    hipLaunchKernelGGL(edge_stored_dgrad_kernel<true>, gr, b, 0, st, dY, ldg, W2t, ldwt, U, M, k, F1, O, scale1, shift1, mean1, invstd1, slope, md, mean3,
+                       invstd3, dU, G3, partials_u, partials_3);
+  else
+    hipLaunchKernelGGL(edge_stored_dgrad_kernel<false>, gr, b, 0, st, dY, ldg, W2t, ldwt, U, M, k, F1, O, scale1, shift1, mean1, invstd1, slope, md, mean3,
+                       invstd3, dU, G3, partials_u, partials_3);
   return spgan_launch_status();
 }

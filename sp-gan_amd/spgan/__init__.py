@@ -9,12 +9,12 @@ absence is a hard error (there is no CPU fallback).
 from . import dataset, edge_conv, edge_max, edge_rank, edge_weight, edge_window, fixture_rng, metrics, ops, pointconv_util, pointnet_util, sampling  # noqa: F401
 from .capture import CapturedBody                                          # noqa: F401
 from .losses import GradientPenalty, dis_loss, gen_loss                    # noqa: F401
-from .modules import (AdaptivePointNorm, Discriminator, EdgeBlock, Generator, conv2dbr, deform_edgeConv, deform_edgeConv_feat,   # noqa: F401
-                      deform_edgeConv_first, deform_edgeConv_simple, edgeConv, get_edge_features, get_edge_features_xyz, upsample_edgeConv)
+from .modules import (AdaptivePointNorm, Discriminator, EdgeBlock, Generator, bilateral_upsample_edgeConv, conv2dbr, deform_edgeConv,   # noqa: F401
+                      deform_edgeConv_feat, deform_edgeConv_first, deform_edgeConv_simple, edgeConv, get_edge_features, get_edge_features_xyz, upsample_edgeConv)
 from .optim import EMA, Adam, StepLR, flatten_module                       # noqa: F401
 from .parallel import DataParallel, init_process_group_from_env, shard_batch   # noqa: F401
 from .train import TrainStep, requires_grad                                # noqa: F401
 
 __all__ = ["Generator", "Discriminator", "EdgeBlock", "AdaptivePointNorm", "get_edge_features", "edgeConv", "conv2dbr", "upsample_edgeConv", "get_edge_features_xyz", "deform_edgeConv_simple",
-           "deform_edgeConv_first", "deform_edgeConv_feat", "deform_edgeConv", "dis_loss", "gen_loss",
+           "deform_edgeConv_first", "deform_edgeConv_feat", "deform_edgeConv", "bilateral_upsample_edgeConv", "dis_loss", "gen_loss",
            "GradientPenalty", "TrainStep", "CapturedBody", "Adam", "EMA", "StepLR", "DataParallel", "requires_grad", "ops", "fixture_rng", "sampling"]

@@ -302,6 +302,9 @@ SIGNATURES = {
     "spgan_edge_weight_dgrad": (I, [P, I, P, I, P, I, P, I, I, I, I, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, P]),
     "spgan_edge_weight_gather2": (I, [P, I, P, I, P, I, I, I, P, P, P, P, F, P, P]),
     "spgan_edge_weight_split": (I, [P, P, I, P, I, P, I, I, I, P, P, P, P, P, P, P, P, F, P, P, P, P, P]),
+    "spgan_edge_stored_gemm": (I, [P, I, I, I, P, P, F, P, P, P, P, P, P, I, P, I, P, I, P, P]),
+    "spgan_edge_stored_wgrad": (I, [P, I, I, I, P, P, F, P, P, P, P, P, P, I, I, P, I, P, SZ, P]),
+    "spgan_edge_stored_dgrad": (I, [P, I, P, I, P, I, I, I, I, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, P]),
     "spgan_nn_distance": (I, [P, P, I, I, I, P, P, P]),
     "spgan_chamfer_bwd": (I, [P, P, I, I, I, P, P, P, P, P, P]),
     "spgan_chamfer_pairs": (I, [P, P, I, I, I, I, P, P]),

@@ -1,5 +1,5 @@
 """The gather-side edge convolutions: the autograd Functions behind `spgan.edgeConv`, `upsample_edgeConv`, `deform_edgeConv_simple` /
-`_first`, `deform_edgeConv_feat` and `deform_edgeConv`, over the launchers of spgan.edge_max / edge_window / edge_rank / edge_weight.
+`_first`, `deform_edgeConv_feat`, `deform_edgeConv` and `bilateral_upsample_edgeConv`, over the launchers of spgan.edge_max / edge_window / edge_rank / edge_weight.
 
 The family's conventions, stated once:
 * A 1x1 convolution over the edge features cat[x_i, x_j - x_i] is one per-point GEMM, PQ [M,2F] = [P | Q] = x.[Wd ; Wc - Wd]^T + [0 ; b]
@@ -12,7 +12,7 @@ The family's conventions, stated once:
   statistics that ARE updated in place are not read by the backward.
 * Once differentiable: a selection or a mask is piecewise constant and the backward is a closed form over saved statistics, so a second
   derivative is refused where it is asked for (`refuse_double_backward`): no GradientPenalty on top of these layers.
-* The rank layers (RankEdgeConvFn's [1,k] product, all of WeightedRankEdgeConvFn and CoordRankEdgeConvFn) compute exact fp32 products: they do not follow
+* The rank layers (RankEdgeConvFn's [1,k] product, all of WeightedRankEdgeConvFn, CoordRankEdgeConvFn and BilateralUpsampleEdgeConvFn) compute exact fp32 products: they do not follow
   ops.set_mfma_operands.
 * Weight-derived operand images are cached per weight set (`cached_images`)."""
 from __future__ import annotations
@@ -30,7 +30,7 @@ Tensor = torch.Tensor
 
 # ----------------------------------------------------------------------------- operand images
 # one dictionary per builder: a layer that reaches the cap does not evict another layer's images
-_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}, "coord": {}}
+_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}, "coord": {}, "bilateral": {}}
 
 
 def cached_images(cache: Dict[tuple, tuple], weights: Sequence[Tensor], extra: tuple, build: Callable):
@@ -131,6 +131,51 @@ def coord_images(Wh: Tensor, Wf: Tensor, Wx: Tensor, Wa2: Tensor, Wa3: Tensor, W
         return (Wst_h, Wst_f, Wst_x, torch.cat([Wst_h, Wst_f], dim=0).t().contiguous(), Wst_x.t().contiguous(), Wm2.contiguous(), Wm2.t().contiguous(),
                 Wm3.contiguous(), Wm3.t().contiguous(), W2i, W2i.t().contiguous())
     return cached_images(_IMAGES["coord"], (Wh, Wf, Wx, Wa2, Wa3, W2), (), build)
+
+
+def parity_major(t: Tensor, dim: int = 0) -> Tensor:
+    """inte_conv_hk's 4C output channels o = 2c' + h along `dim` -> the order o' = h*2C + c' (the bilateral layer's: the [M*T, 4C] rows (i,t)
+    then read as [M, k, 2C] rows (i, r' = 2t + h))"""
+    n = t.shape[dim] // 2
+    return t.unflatten(dim, (n, 2)).transpose(dim, dim + 1).flatten(dim, dim + 1)
+
+
+def channel_major(t: Tensor, dim: int = 0) -> Tensor:
+    """the inverse of parity_major: o' = h*2C + c' along `dim` -> o = 2c' + h"""
+    n = t.shape[dim] // 2
+    return t.unflatten(dim, (2, n)).transpose(dim, dim + 1).flatten(dim, dim + 1)
+
+
+def paired_ranks(idx: Tensor) -> Tensor:
+    """idx [M,k] -> idxp with idxp[i, 2t + h] = idx[i, h*T + t], T = k/2: the rank order in which the bilateral layer's weight branch runs"""
+    M, k = idx.shape
+    return idx.view(M, 2, k // 2).transpose(1, 2).reshape(M, k)
+
+
+def bilateral_images(W1: Tensor, Wf: Tensor, Wx: Tensor, Wa2: Tensor, Wa3: Tensor, V: Tensor, C: int, k: int):
+    """The operand images of bilateral_upsample_edgeConv's six conv weights (inte_conv_hk.0 [4C,2C,1,w], conv_fea.0 [16,2C,1,1], conv_xyz.0
+    [16,6,1,1], conv_all.0 [64,16,1,1], conv_all.3 [2C,64,1,1], conv2.conv [F2,2C,1,2k]):
+    (Wc1 [4C,C], Wd1 [4C,w*C], Wd1^T -- upsample_images' with the output channels in the order o' = h*2C + c' (parity_major) --, Vc [F2,C],
+    Vd [F2,k*C], Vd^T, Vc^T, V2i [F2, k*2C] = conv2's last k taps with column r'*2C + c' = tap k + j, r' = 2t + h, j = h*T + t, V2i^T,
+    Wst_f [32,C], Wst_x [32,3], Wst_x^T, Wcat_t [C, 4C+32] = [Wc1 ; Wst_f]^T, Wm2 [64,16], Wm2^T, Wm3 [2C,64], Wm3^T).
+    Cached per weight set (cached_images)."""
+    def build(W1, Wf, Wx, Wa2, Wa3, V):
+        w = W1.shape[3]
+        T = k - w + 1
+        F2 = V.shape[0]
+        W1p = parity_major(W1)
+        Wc1 = W1p[:, :C, 0, :].sum(dim=2)
+        Wd1 = W1p[:, C:, 0, :].permute(0, 2, 1).reshape(4 * C, w * C)
+        Vc = V[:, :C, 0, :k].sum(dim=2)
+        Vd = V[:, C:, 0, :k].permute(0, 2, 1).reshape(F2, k * C)
+        V2i = V[:, :, 0, k:].reshape(F2, 2 * C, 2, T).permute(0, 3, 2, 1).reshape(F2, k * 2 * C)
+        Wst_f, Wst_x = stacked(Wf), stacked(Wx)
+        Wm2, Wm3 = Wa2.reshape(Wa2.shape[0], Wa2.shape[1]), Wa3.reshape(Wa3.shape[0], Wa3.shape[1])
+        Wd1, Vd, V2i = Wd1.contiguous(), Vd.contiguous(), V2i.contiguous()          # C = 1: the reshapes above are strided views
+        return (Wc1, Wd1, Wd1.t().contiguous(), Vc, Vd, Vd.t().contiguous(), Vc.t().contiguous(), V2i, V2i.t().contiguous(), Wst_f, Wst_x,
+                Wst_x.t().contiguous(), torch.cat([Wc1, Wst_f], dim=0).t().contiguous(), Wm2.contiguous(), Wm2.t().contiguous(), Wm3.contiguous(),
+                Wm3.t().contiguous())
+    return cached_images(_IMAGES["bilateral"], (W1, Wf, Wx, Wa2, Wa3, V), (C, k), build)
 
 
 # ----------------------------------------------------------------------------- what the Functions share
@@ -621,3 +666,145 @@ class CoordRankEdgeConvFn(Function):
         db2 = dbias(dy, train) if need[24] else None
         return (None, dx, dpc, dWh, dbh) + gb(sumsh, need, 5) + (dWf, dbf) + gb(sumsf, need, 9) + (dWx, dbx) + gb(sumsx, need, 13) + \
             (dWa2, dba2) + gb(sums2, need, 17) + (dWa3, dba3) + gb(sums3, need, 21) + (dW2, db2) + gb(sumsc, need, 25)
+
+
+class BilateralUpsampleEdgeConvFn(Function):
+    """out [B,Fout,2N] = the reference's bilateral_upsample_edgeConv (Generation/modules.py:847-925): upsample_edgeConv whose interpolated
+    tensor lrelu(bn1(inte_conv_hk(e))) is multiplied, element by element, by deform_edgeConv's weight s = softmax over the k ranks of
+    conv_all(conv_fea(e) * conv_xyz(y)) (2C channels) before conv2 reads it as its taps k..2k-1.
+    inte_conv_hk's output channels are computed in the order o' = h*2C + c' (bilateral_images), so that the pre-norm U [M*T, 4C] with rows
+    (i,t) is also [M, k, 2C] with rows (i, r' = 2t + h); the weight branch runs over the graph in that rank order (paired_ranks), so that its
+    pre-norm output z3 [M*k, 2C] has the same rows.  The product Y3 = (lrelu(bn1(U)) * s).flat V2i^T forms its A operand in LDS from U, z3
+    and the softmax normaliser (edge_weight.edge_stored_gemm); the activated tensor, s and their product are never stored.
+    Forward keeps U and z3 (two edge-sized tensors, E = 4 M k 2C bytes each) beside w0 [M*k,16] and z2 [M*k,64]; the backward adds gU / dU
+    and g3 / dz3 and the window dgrad's S (E/2)  (DESIGN.md section 23).
+    holder: softmax, slope, bns = the six nn.BatchNorm2d modules (inte, fea, xyz, all.1, all.4, conv2); parameters of inte_conv_hk, conv_fea,
+    conv_xyz, conv_all.0/1, conv_all.3/4 and conv2.  Differentiable in x, pc and every parameter."""
+
+    @staticmethod
+    def forward(ctx, h, x, pc, *params):
+        W1, b1, g1, be1, Wf, bf, gf, bef, Wx, bx, gx, bex, Wa2, ba2, g2, be2, Wa3, ba3, g3, be3, V, b2, gc, bec = params
+        B, C, N = x.shape
+        k, M, train = h.k, B * N, h.training
+        T, E = k // 2, M * k
+        x_pm, pc_pm = ops.cm_to_pm(x), ops.cm_to_pm(pc)
+        idx = h.idx if h.idx is not None else ops.knn(x_pm, B, N, k, h.knn_mode)
+        idxp = paired_ranks(idx)
+        Wc1, Wd1, _, Vc, Vd, _, _, V2i, _, Wst_f, Wst_x, _, _, Wm2, _, Wm3, _ = bilateral_images(W1, Wf, Wx, Wa2, Wa3, V, C, k)
+        # exact=True: fp32 operands whatever ops.set_mfma_operands selected
+        Q1 = ops.gemm_nt(x_pm, Wc1, parity_major(b1.detach()), exact=True)
+        U, rec = split_records(edge_window.edge_window_gemm(x_pm, idx, Wd1, rowadd=Q1, stats=train), train)
+        del Q1
+        if train:                                          # the module's BatchNorm keeps the reference's channel order
+            rec = (channel_major(rec[0], 1),) + tuple(rec[1:])
+        st1 = parity_major(bn_stats(h.bns[0], train, M * T, g1, be1, records=rec), 1)
+        del rec
+        PQf = ops.gemm_nt(x_pm, Wst_f, pq_bias(bf), exact=True)
+        PQx = ops.gemm_nt(pc_pm, Wst_x, pq_bias(bx), exact=True)
+        stf = bn_stats(h.bns[1], train, E, gf, bef, records=edge_records(PQf, idx) if train else None)
+        stx = bn_stats(h.bns[2], train, E, gx, bex, records=edge_records(PQx, idx) if train else None)
+        w0 = edge_weight.edge_weight_gather2(PQf, PQx, idxp, stf[0], stf[1], stx[0], stx[1], h.slope)
+        if train:
+            z2, m, v = ops.gemm_nt(w0, Wm2, ba2, stats=True, exact=True)
+            st2 = bn_stats(h.bns[3], True, E, g2, be2, moments=(m, v))
+            z3, m, v = ops.gemm_nt(z2, Wm3, ba3, pro=(st2[0], st2[1], h.slope), stats=True, exact=True)
+            st3 = bn_stats(h.bns[4], True, E, g3, be3, moments=(m, v))
+        else:
+            st2 = bn_stats(h.bns[3], False, E, g2, be2)
+            z2 = ops.gemm_nt(w0, Wm2, ba2, exact=True)
+            st3 = bn_stats(h.bns[4], False, E, g3, be3)
+            z3 = ops.gemm_nt(z2, Wm3, ba3, pro=(st2[0], st2[1], h.slope), exact=True)
+        norm = edge_weight.edge_weight_norm(z3, k, st3[0], st3[1], h.slope) if h.softmax else None
+        Y3 = edge_weight.edge_stored_gemm(U, k, st1[0], st1[1], z3, st3[0], st3[1], norm, V2i, slope=h.slope)
+        Q2 = ops.gemm_nt(x_pm, Vc, b2, exact=True)
+        Y, rec = split_records(edge_window.edge_window_gemm(x_pm, idx, Vd, rowadd=Q2, add2=Y3, stats=train), train)
+        stc = bn_stats(h.bns[5], train, M, gc, bec, records=rec)
+        del Q2, Y3, rec
+        out_pm = ops.affine_act(Y, stc[0], stc[1], 0.0)
+        h.last_idx = idx
+        ctx.h, ctx.st, ctx.norm = h, (st1, stf, stx, st2, st3, stc), norm
+        ctx.save_for_backward(x, pc, U, PQf, PQx, w0, z2, z3, Y, idx, W1, Wf, Wx, Wa2, Wa3, V, g1, g2, g3, gc)
+        return ops.pm_to_cm(out_pm, B, N).view(B, V.shape[0] // 2, 2 * N)          # out[b, f, s*N + n] = y[b, 2f+s, n]: a view
+
+    @staticmethod
+    def backward(ctx, dout):
+        refuse_double_backward("bilateral_upsample_edgeConv")
+        return BilateralUpsampleEdgeConvFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        x, pc, U, PQf, PQx, w0, z2, z3, Y, idx, W1, Wf, Wx, Wa2, Wa3, V, g1, g2, g3, gc = ctx.saved_tensors
+        h = ctx.h
+        B, C, N = x.shape
+        k, M, train = h.k, B * N, h.training
+        w = W1.shape[3]
+        T, E = k // 2, M * k
+        F2, F1, Fm, Fw = V.shape[0], Wf.shape[0], Wa2.shape[0], 2 * C
+        (sc1, sh1, inv1, mu1), stf, stx, (sc2, sh2, inv2, mu2), (sc3, sh3, inv3, mu3), stc = ctx.st
+        need = ctx.needs_input_grad
+        _, _, Wd1t, _, _, Vdt, Vct, _, V2it, _, _, Wst_xt, Wcat_t, _, Wm2t, _, Wm3t = bilateral_images(W1, Wf, Wx, Wa2, Wa3, V, C, k)
+        x_pm = ops.cm_to_pm(x)
+        idxp = paired_ranks(idx)
+        dy, sumsc = relu_bn_bwd(dout, Y, stc, gc, h)
+        # the product act(U) * s, both LeakyReLUs and the softmax: gU and gz3 [M,k,2C] are the two per-edge buffers of the backward
+        gU, sums1, gz3, sums3 = edge_weight.edge_stored_dgrad(dy, V2it, U, k, sc1, sh1, mu1, inv1, z3, sc3, sh3, mu3, inv3, ctx.norm, h.slope)
+        # the weight MLP, last layer first
+        dz3 = ops.bn_bwd_apply(gz3, z3, mu3, inv3, g3, used(sums3, train), E)
+        del gz3
+        dWa3 = ops.gemm_tn(dz3, z2, pro=(sc2, sh2, h.slope), exact=True).view(Fw, Fm, 1, 1) if need[19] else None
+        dba3 = dbias(dz3, train) if need[20] else None
+        gz2, t1, t2 = ops.gemm_nt_bnbwd(dz3, Wm3t, z2, sc2, sh2, mu2, inv2, h.slope, exact=True)
+        del dz3
+        sums2 = torch.cat([t1, t2])
+        dz2 = ops.bn_bwd_apply(gz2, z2, mu2, inv2, g2, used(sums2, train), E)
+        del gz2
+        dWa2 = ops.gemm_tn(dz2, w0, exact=True).view(Fm, F1, 1, 1) if need[15] else None
+        dba2 = dbias(dz2, train) if need[16] else None
+        dw0 = ops.gemm_nt(dz2, Wm2t, exact=True)
+        del dz2
+        gf_, sumsf, gx_, sumsx = edge_weight.edge_weight_split(dw0, PQf, PQx, idxp, stf[0], stf[1], stf[3], stf[2], stx[0], stx[1], stx[3], stx[2],
+                                                               h.slope)
+        del dw0
+        rowptr, src = ops.csr_build(idxp, B, N)
+        dPQf = rank_scatter(gf_, rowptr, src, stf, PQf, idxp, sumsf, train)
+        del gf_
+        dPQx = rank_scatter(gx_, rowptr, src, stx, PQx, idxp, sumsx, train)
+        del gx_
+        # LeakyReLU + BatchNorm of inte_conv_hk, in the channel order o' of U
+        dU = ops.bn_bwd_apply(gU.view(M * T, 4 * C), U, mu1, inv1, parity_major(g1.detach()), used(sums1, train), M * T)
+        del gU
+        dQ1 = ops.colsum(dU, T)                                            # [M,4C]: the central half sees the sum over the window positions
+        dV = None
+        if need[23]:
+            dV = torch.empty_like(V)
+            dV[:, :C, 0, :k] = ops.gemm_tn(dy, x_pm, exact=True).unsqueeze(2)
+            dV[:, C:, 0, :k] = edge_window.edge_window_wgrad(x_pm, idx, dy, k).view(F2, k, C).permute(0, 2, 1)
+            dV2i = edge_weight.edge_stored_wgrad(U, k, sc1, sh1, z3, sc3, sh3, ctx.norm, dy, h.slope)
+            dV[:, :, 0, k:] = dV2i.view(F2, T, 2, 2 * C).permute(0, 3, 2, 1).reshape(F2, 2 * C, k)
+        dW1 = None
+        if need[3]:
+            dW1p = torch.empty((4 * C, 2 * C, 1, w), dtype=torch.float32, device=x.device)
+            dW1p[:, :C, 0, :] = ops.gemm_tn(dQ1, x_pm, exact=True).unsqueeze(2)
+            dW1p[:, C:, 0, :] = edge_window.edge_window_wgrad(x_pm, idx, dU, w).view(4 * C, w, C).permute(0, 2, 1)
+            dW1 = channel_major(dW1p)
+        dx = None
+        if need[1]:
+            S = edge_window.edge_window_dgrad(dU, Wd1t, k, C)              # [M,k,C]
+            edge_window.edge_window_dgrad(dy, Vdt, k, C, out=S)
+            rowptr, src = ops.csr_build(idx, B, N)
+            # both per-point products of the inte and the conv_fea branch in one: [dQ1 | dPQf] [Wc1 ; Wst_f]
+            dx_pm = edge_window.edge_window_scatter(S, rowptr, src, ops.gemm_nt(dy, Vct, exact=True),
+                                                    ops.gemm_nt(torch.cat([dQ1, dPQf], dim=1), Wcat_t, exact=True))
+            del S
+            dx = ops.pm_to_cm(dx_pm, B, N)
+        dWf = unstacked_grad(ops.gemm_tn(dPQf, x_pm, exact=True)) if need[7] else None
+        dWx = unstacked_grad(ops.gemm_tn(dPQx, ops.cm_to_pm(pc), exact=True)) if need[11] else None
+        dpc = ops.pm_to_cm(ops.gemm_nt(dPQx, Wst_xt, exact=True), B, N) if need[2] else None
+        db1 = channel_major(dbias(dU, train)) if need[4] else None
+        dbf = dbias(dPQf[:, F1:], train) if need[8] else None
+        dbx = dbias(dPQx[:, F1:], train) if need[12] else None
+        db2 = dbias(dy, train) if need[24] else None
+        s1 = channel_major(sums1.view(2, 4 * C), 1).reshape(-1)           # [sum g | sum g*uhat], each back in the module's channel order
+        return (None, dx, dpc, dW1, db1) + gb(s1, need, 5) + (dWf, dbf) + gb(sumsf, need, 9) + (dWx, dbx) + gb(sumsx, need, 13) + \
+            (dWa2, dba2) + gb(sums2, need, 17) + (dWa3, dba3) + gb(sums3, need, 21) + (dV, db2) + gb(sumsc, need, 25)

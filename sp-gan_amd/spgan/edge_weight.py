@@ -1,6 +1,7 @@
 """Tensor-level wrappers of the weighted full-rank edge convolution's launchers (csrc/edge_rank.hip; include/spgan_hip.h): the passes behind
 `spgan.deform_edgeConv_feat` (edge_conv.WeightedRankEdgeConvFn) and, with the two-branch passes at the end, `spgan.deform_edgeConv`
-(edge_conv.CoordRankEdgeConvFn).  PQ, idx, scale1 / shift1 and W2i as in spgan.edge_rank; the per-edge weight
+(edge_conv.CoordRankEdgeConvFn); the stored-operand forms at the end serve `spgan.bilateral_upsample_edgeConv`
+(edge_conv.BilateralUpsampleEdgeConvFn).  PQ, idx, scale1 / shift1 and W2i as in spgan.edge_rank; the per-edge weight
 s(i,r,c) is the softmax over the k ranks of a3 = lrelu(scale3*z3 + shift3) with z3 [M*k, F1] the stored pre-norm output of the weight MLP
 and norm = (wmax, wrs) [M,F1] x 2 its per-(point, channel) normaliser (edge_weight_norm); norm=None: s = a3 (softmax=False).
 h, s and h*s exist only inside the kernels.  Exact fp32 MFMA products, as spgan.edge_rank."""
@@ -14,7 +15,7 @@ from . import _lib
 from ._lib import check
 from .edge_max import tile_sums
 from .edge_rank import K_MAX, SLOPE, Norm, _dgrad_sizes, _graph, _mod, edge_rank_gemm, edge_rank_wgrad, tile_points
-from .ops import _f32, _ld, _p, _s, _vec
+from .ops import _f32, _ld, _p, _rowmajor2d, _s, _vec
 
 Tensor = torch.Tensor
 
@@ -106,3 +107,84 @@ def edge_weight_split(dw0: Tensor, PQa: Tensor, PQb: Tensor, idx: Tensor, scale_
                                               v(mean_b, "mean_b"), v(invstd_b, "invstd_b"), float(slope), _p(ga), _p(gb), _p(part[0]), _p(part[1]),
                                               _s()), "edge_weight_split", M=M_, k=k, F=F_)
     return ga, tile_sums(part[0], M_, tp), gb, tile_sums(part[1], M_, tp)
+
+
+# ----------------------------------------------------------------------------- the stored-operand forms (bilateral_upsample_edgeConv)
+STORED_K_MAX = 28
+
+
+def _stored(U: Tensor, z3: Tensor, k: int):
+    """U and z3 hold [M,k,F1] values each, contiguous, in any view of that memory (U is upsample_edgeConv's [M*k/2, 2*F1]) -> (M, F1)"""
+    _f32(U, "U"); _f32(z3, "z3", 2)
+    if k % 2 or not 2 <= k <= STORED_K_MAX:
+        raise ValueError("edge_stored: k must be even and lie in 2..%d, got k=%d" % (STORED_K_MAX, k))
+    if not z3.is_contiguous() or z3.shape[0] % k or z3.shape[0] < k or not U.is_contiguous() or U.numel() != z3.numel():
+        raise ValueError("edge_stored: z3 must be contiguous [M*k, F1] and U hold as many contiguous values, got %s and %s (k=%d)"
+                         % (tuple(z3.shape), tuple(U.shape), k))
+    return z3.shape[0] // k, z3.shape[1]
+
+
+def edge_stored_gemm(U: Tensor, k: int, scale1: Tensor, shift1: Tensor, z3: Tensor, scale3: Tensor, shift3: Tensor, norm: Norm, W2i: Tensor,
+                     b2: Optional[Tensor] = None, stats: bool = False, slope: float = SLOPE):
+    """y [M,O] = b2 + (h*s).flat @ W2i^T with h(i,r,c) = lrelu(scale1[(r&1)*F1 + c] * U[i,r,c] + shift1[(r&1)*F1 + c]): edge_weight_gemm
+    whose modulated operand is the stored pre-norm tensor U [M,k,F1]; scale1, shift1 [2*F1]; W2i [O, k*F1], column r*F1 + c.
+    (-> (y, partials, tile_rows) with stats=True)"""
+    M_, F1 = _stored(U, z3, k)
+    _rowmajor2d(W2i, "W2i")
+    if W2i.shape[1] != k * F1 or W2i.shape[0] < 1:
+        raise ValueError("W2i must be [O, k*F1] = [O, %d] (k=%d, F1=%d), got %s" % (k * F1, k, F1, tuple(W2i.shape)))
+    O = W2i.shape[0]
+    md = _mod((z3, scale3, shift3, norm), M_, k, F1)
+    y = torch.empty((M_, O), dtype=torch.float32, device=U.device)
+    part, tp = None, 0
+    if stats:
+        tp = tile_points(k)
+        part = torch.empty(((M_ + tp - 1) // tp, O, 2), dtype=torch.float32, device=U.device)
+    check(_lib.load().spgan_edge_stored_gemm(_p(U), M_, k, F1, _p(_vec(scale1, 2 * F1, "scale1")), _p(_vec(shift1, 2 * F1, "shift1")), float(slope), *md,
+                                             _p(W2i), _ld(W2i), _p(_vec(b2, O, "b2")), O, _p(y), O, _p(part), _s()), "edge_stored_gemm",
+          M=M_, k=k, F1=F1, O=O)
+    return (y, part, tp) if stats else y
+
+
+def edge_stored_wgrad(U: Tensor, k: int, scale1: Tensor, shift1: Tensor, z3: Tensor, scale3: Tensor, shift3: Tensor, norm: Norm, dy: Tensor,
+                      slope: float = SLOPE) -> Tensor:
+    """dW2i [O, k*F1] = dy^T @ (h*s).flat over the stored h (edge_stored_gemm)"""
+    M_, F1 = _stored(U, z3, k)
+    _rowmajor2d(dy, "dy")
+    if dy.shape[0] != M_:
+        raise ValueError("dy must have M = %d rows" % M_)
+    O = dy.shape[1]
+    md = _mod((z3, scale3, shift3, norm), M_, k, F1)
+    lib = _lib.load()
+    wsb = lib.spgan_edge_rank_wgrad_ws_bytes(M_, k, F1, O)
+    if wsb == 0:
+        raise ValueError("edge_stored_wgrad: unsupported sizes M=%d k=%d F1=%d O=%d" % (M_, k, F1, O))
+    ws = torch.empty((wsb // 4,), dtype=torch.float32, device=U.device)
+    dW = torch.empty((O, k * F1), dtype=torch.float32, device=U.device)
+    check(lib.spgan_edge_stored_wgrad(_p(U), M_, k, F1, _p(_vec(scale1, 2 * F1, "scale1")), _p(_vec(shift1, 2 * F1, "shift1")), float(slope), *md,
+                                      _p(dy), _ld(dy), O, _p(dW), k * F1, _p(ws), wsb, _s()), "edge_stored_wgrad", M=M_, k=k, F1=F1, O=O)
+    return dW
+
+
+def edge_stored_dgrad(dy: Tensor, W2t: Tensor, U: Tensor, k: int, scale1: Tensor, shift1: Tensor, mean1: Tensor, invstd1: Tensor, z3: Tensor,
+                      scale3: Tensor, shift3: Tensor, mean3: Tensor, invstd3: Tensor, norm: Norm, slope: float = SLOPE):
+    """-> (gU [M,k,F1], sums_u [2*2F1] = [sum gU | sum gU*uhat], one entry per (rank parity, channel) as scale1 is laid out, g3 [M*k, F1],
+    sums_3 [2*F1]): edge_weight_dgrad over the stored h.  W2t [k*F1, O] = W2i transposed; scale1, shift1, mean1, invstd1 [2*F1]."""
+    M_, F1 = _stored(U, z3, k)
+    _rowmajor2d(dy, "dy"); _rowmajor2d(W2t, "W2t")
+    O = dy.shape[1]
+    if dy.shape[0] != M_ or tuple(W2t.shape) != (k * F1, O):
+        raise ValueError("dy must be [M,O] and W2t [k*F1, O] = [%d, %d], got %s and %s" % (k * F1, O, tuple(dy.shape), tuple(W2t.shape)))
+    tp = tile_points(k)
+    tiles = (M_ + tp - 1) // tp
+    md = _mod((z3, scale3, shift3, norm), M_, k, F1)
+    gU = torch.empty((M_, k, F1), dtype=torch.float32, device=U.device)
+    g3 = torch.empty((M_ * k, F1), dtype=torch.float32, device=U.device)
+    part_u = torch.empty((tiles, 2 * F1, 2), dtype=torch.float32, device=U.device)
+    part_3 = torch.empty((tiles, F1, 2), dtype=torch.float32, device=U.device)
+    v1 = lambda t, n: _p(_vec(t, 2 * F1, n))
+    check(_lib.load().spgan_edge_stored_dgrad(_p(dy), _ld(dy), _p(W2t), _ld(W2t), _p(U), M_, k, F1, O, v1(scale1, "scale1"), v1(shift1, "shift1"),
+                                              v1(mean1, "mean1"), v1(invstd1, "invstd1"), float(slope), md[0], md[1], md[2],
+                                              _p(_vec(mean3, F1, "mean3")), _p(_vec(invstd3, F1, "invstd3")), md[3], md[4], _p(gU), _p(g3),
+                                              _p(part_u), _p(part_3), _s()), "edge_stored_dgrad", M=M_, k=k, F1=F1, O=O)
+    return gU, tile_sums(part_u, M_, tp), g3, tile_sums(part_3, M_, tp)

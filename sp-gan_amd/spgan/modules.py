@@ -930,3 +930,72 @@ class deform_edgeConv(nn.Module):
         out = edge_conv.CoordRankEdgeConvFn.apply(h, x.contiguous(), pc.contiguous(), *params)
         self.last_idx = h.last_idx
         return out
+
+
+class bilateral_upsample_edgeConv(nn.Module):
+    """Generation/modules.py:847-925: [B,Fin,N] x [B,3,N] -> [B,Fout,2N], the point-doubling edge convolution with a coordinate-guided
+    weight: conv2(cat(e, reshuffled inte_conv_hk(e) * w)) with (e, y) = get_edge_features_xyz(x, pc), inte_conv_hk = Conv2d(2Fin -> 4Fin,
+    [1, k/2+1]) + BatchNorm2d + LeakyReLU as in upsample_edgeConv, w = conv_all(conv_fea(e) * conv_xyz(y)) -- conv_fea 2Fin -> 16, conv_xyz
+    6 -> 16, conv_all 16 -> 64 -> 2Fin, each Conv2d 1x1 + BatchNorm2d + LeakyReLU -- normalised by a softmax over the k neighbours
+    (softmax=True), and conv2 = conv2dbr(2Fin -> 2Fout, [1,2k]).  Evaluated by edge_conv.BilateralUpsampleEdgeConvFn (csrc/edge_window.hip,
+    csrc/edge_rank.hip): neither edge tensor, the activated interpolation, the weight, their product nor the merged [B,2Fin,N,2k] tensor
+    exist in forward or backward; the forward keeps two [B*N,k,2Fin] tensors.  The sub-modules are parameter containers in the reference's
+    order and names (state_dicts load strictly both ways); num is kept and unused, as in the reference.
+    idx (an extension, as edgeConv's): the graph to use instead of the kNN graph of x, int64 [B, N*k] local indices (range-checked outside
+    a capture) or int32 [B*N,k] global rows (trusted).  k even, 2 <= k <= 28.  Once differentiable in x, pc and the parameters.  last_idx:
+    the graph of the latest forward."""
+
+    def __init__(self, Fin, Fout, k, num, softmax=True):
+        super().__init__()
+        if k % 2 or not 2 <= k <= 28:
+            raise ValueError("bilateral_upsample_edgeConv: k must be even and lie in 2..28 (the reference's view of the [.., k/2] tensor as "
+                             "[.., k] fails for an odd k), got k=%d (Fin=%d, Fout=%d)" % (k, Fin, Fout))
+        if Fin < 1 or Fout < 1:
+            raise ValueError("bilateral_upsample_edgeConv: Fin and Fout must be positive, got Fin=%d, Fout=%d" % (Fin, Fout))
+        self.k = k
+        self.Fin = Fin
+        self.Fout = Fout
+        self.softmax = softmax
+        self.num = num
+        self.conv2 = conv2dbr(2 * Fin, 2 * Fout, [1, 2 * k], [1, 1])
+        self.conv_xyz = nn.Sequential(
+            nn.Conv2d(6, 16, 1),
+            nn.BatchNorm2d(16),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.conv_fea = nn.Sequential(
+            nn.Conv2d(2 * Fin, 16, 1),
+            nn.BatchNorm2d(16),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.conv_all = nn.Sequential(
+            nn.Conv2d(16, 64, 1),
+            nn.BatchNorm2d(64),
+            nn.LeakyReLU(inplace=True),
+            nn.Conv2d(64, 2 * Fin, 1),
+            nn.BatchNorm2d(2 * Fin),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.inte_conv_hk = nn.Sequential(
+            nn.Conv2d(2 * Fin, 4 * Fin, [1, k // 2 + 1], [1, 1]),
+            nn.BatchNorm2d(4 * Fin),
+            nn.LeakyReLU(inplace=True)
+        )
+        self.last_idx: Optional[torch.Tensor] = None
+
+    def forward(self, x, pc, idx: Optional[torch.Tensor] = None):
+        name = "bilateral_upsample_edgeConv"
+        layers = [(self.inte_conv_hk[0], self.inte_conv_hk[1]), (self.conv_fea[0], self.conv_fea[1]), (self.conv_xyz[0], self.conv_xyz[1]),
+                  (self.conv_all[0], self.conv_all[1]), (self.conv_all[3], self.conv_all[4]), (self.conv2.conv, self.conv2.bn)]
+        slopes = {float(a.negative_slope) for a in (self.inte_conv_hk[2], self.conv_fea[2], self.conv_xyz[2], self.conv_all[2], self.conv_all[5])}
+        B, N, idx, knn_mode = check_edge_input(name, x, idx, self.k, self.Fin, self.Fout, [bn for _, bn in layers],
+                                               None if len(slopes) == 1 else "the five LeakyReLUs must share one slope, got %s" % sorted(slopes))
+        _require_gpu(pc, name + " pc")
+        if pc.dim() != 3 or pc.shape[0] != B or pc.shape[1] != 3 or pc.shape[2] != N:
+            raise ValueError("%s: pc must be [B,3,N] for x [B,C,N], got %s and %s" % (name, tuple(pc.shape), tuple(x.shape)))
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, softmax=bool(self.softmax), idx=idx, knn_mode=knn_mode,
+                    slope=slopes.pop(), bns=tuple(bn for _, bn in layers), last_idx=None)
+        params = [t for conv, bn in layers for t in (conv.weight, conv.bias, bn.weight, bn.bias)]
+        out = edge_conv.BilateralUpsampleEdgeConvFn.apply(h, x.contiguous(), pc.contiguous(), *params)
+        self.last_idx = h.last_idx
+        return out
