@@ -817,6 +817,33 @@ int spgan_edge_stored_dgrad(const float* dY, int ldg, const float* W2t, int ldwt
                             const float* shift1, const float* mean1, const float* invstd1, float slope, const float* z3, const float* scale3,
                             const float* shift3, const float* mean3, const float* invstd3, const float* wmax, const float* wrs, float* dU,
                             float* G3, float* partials_u, float* partials_3, spgan_stream_t s);
+/* Block tail (csrc/block_tail.hip): what the bilateral / deform blocks (Generation/modules.py:928-1391) put behind their edge convolution --
+ * BatchNorm1d + LeakyReLU over the layer's output and the concatenation with the broadcast global vectors -- as one pass.  All tensors are
+ * float32, channel-major [B, channels, L] contiguous; Y [B,C,L] is the layer's pre-norm output, a "row" the L floats of one (b, c).
+ *   a(b,c,n)    = lrelu(scale[c] * Y[b,c,n] + shift[c], slope)
+ *   gact(b,c,n) = (dout_x[b, Cs+c, n] + dout_g[b, Cg+c, n] + extra[b,c,n]) * lrelu'(scale[c] * Y[b,c,n] + shift[c]);  each of dout_x
+ *                 [B,Cs+C,L], dout_g [B,Cg+C,L], extra [B,C,L] may be NULL (= zeros, never read).
+ *   spgan_cm_stats:              partials [B][C][2] = (sum, M2 about the row's own mean) of every row of Y: the records of
+ *                                spgan_colstats_finalize_bn with tiles = B, G = B*L, tile_rows = L.
+ *   spgan_block_tail_fwd:        out_x [B,Cs+C,L]: channels [0,Cs) = xs[b,c] broadcast over L (xs [B,Cs]), channels Cs + c = a;  out_g
+ *                                [B,Cg+C,L] likewise with g [B,Cg].  Y is read once.  out_x or out_g may be NULL (not both), Cs / Cg may be 0.
+ *   spgan_block_tail_bwd_reduce: partials [B][C][2] = plain sums (sum gact, sum gact * yhat) of every row, yhat = (Y - mean[c]) * invstd[c]
+ *                                (finalize mode 1, tile_rows = L), and in the same launch dxs[b,c] = sum_n dout_x[b,c,n] (c < Cs), dg[b,c] =
+ *                                sum_n dout_g[b,c,n] (c < Cg); dxs / dg NULL: not wanted; zeros where their cotangent is NULL.
+ *   spgan_block_tail_bwd_apply:  dY = gamma * invstd * (gact - sums[c] / count - yhat * sums[C+c] / count) (sums [2C] != NULL: train mode, needs
+ *                                mean, invstd; gamma NULL = 1) or dY = scale * gact (sums == NULL: eval mode).  gact is recomputed by the
+ *                                device function of the reduce pass: the masked gradient is never stored.  dY is distinct from the inputs.
+ * Any B, C, Cs, Cg and L >= 1: one wave walks one row, the grid strides over the rows; rows of L % 4 == 0 floats on 16-byte aligned tensors
+ * move as 16-byte pieces, everything else by scalars (one choice per launch).  No float atomics: results repeat bit for bit. */
+int spgan_cm_stats(const float* Y, int B, int C, int L, float* partials, spgan_stream_t s);
+int spgan_block_tail_fwd(const float* Y, const float* xs, const float* g, int B, int C, int L, int Cs, int Cg, const float* scale,
+                         const float* shift, float slope, float* out_x, float* out_g, spgan_stream_t s);
+int spgan_block_tail_bwd_reduce(const float* Y, const float* dout_x, const float* dout_g, const float* extra, int B, int C, int L, int Cs,
+                                int Cg, const float* scale, const float* shift, float slope, const float* mean, const float* invstd,
+                                float* partials, float* dxs, float* dg, spgan_stream_t s);
+int spgan_block_tail_bwd_apply(const float* Y, const float* dout_x, const float* dout_g, const float* extra, int B, int C, int L, int Cs,
+                               int Cg, const float* scale, const float* shift, float slope, const float* mean, const float* invstd,
+                               const float* gamma, const float* sums, float count, float* dY, spgan_stream_t s);
 /* Per-channel scalar algebra of the double backward, one launch each:
  *   coeffs out4C = [dgammaA | sbarA | xsum0 | xsum1];  phaseb: sums2C = [xsum0+gamma*s0 | xsum1+gamma*s1+invstd*sbarA], dgamma = dgammaA+s1 */
 int spgan_bn_dbl_coeffs(const float* U0, const float* U1, const float* Ugz, const float* S0, const float* S1, const float* gamma,

@@ -305,6 +305,10 @@ SIGNATURES = {
     "spgan_edge_stored_gemm": (I, [P, I, I, I, P, P, F, P, P, P, P, P, P, I, P, I, P, I, P, P]),
     "spgan_edge_stored_wgrad": (I, [P, I, I, I, P, P, F, P, P, P, P, P, P, I, I, P, I, P, SZ, P]),
     "spgan_edge_stored_dgrad": (I, [P, I, P, I, P, I, I, I, I, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "spgan_cm_stats": (I, [P, I, I, I, P, P]),
+    "spgan_block_tail_fwd": (I, [P, P, P, I, I, I, I, I, P, P, F, P, P, P]),
+    "spgan_block_tail_bwd_reduce": (I, [P, P, P, P, I, I, I, I, I, P, P, F, P, P, P, P, P, P]),
+    "spgan_block_tail_bwd_apply": (I, [P, P, P, P, I, I, I, I, I, P, P, F, P, P, P, P, F, P, P]),
     "spgan_nn_distance": (I, [P, P, I, I, I, P, P, P]),
     "spgan_chamfer_bwd": (I, [P, P, I, I, I, P, P, P, P, P, P]),
     "spgan_chamfer_pairs": (I, [P, P, I, I, I, I, P, P]),

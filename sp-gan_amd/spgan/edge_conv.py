@@ -1,5 +1,6 @@
 """The gather-side edge convolutions: the autograd Functions behind `spgan.edgeConv`, `upsample_edgeConv`, `deform_edgeConv_simple` /
-`_first`, `deform_edgeConv_feat`, `deform_edgeConv` and `bilateral_upsample_edgeConv`, over the launchers of spgan.edge_max / edge_window / edge_rank / edge_weight.
+`_first`, `deform_edgeConv_feat`, `deform_edgeConv` and `bilateral_upsample_edgeConv`, over the launchers of spgan.edge_max / edge_window / edge_rank / edge_weight,
+and the tail of the blocks built on them (`BlockTailFn`, over spgan.block_tail).
 
 The family's conventions, stated once:
 * A 1x1 convolution over the edge features cat[x_i, x_j - x_i] is one per-point GEMM, PQ [M,2F] = [P | Q] = x.[Wd ; Wc - Wd]^T + [0 ; b]
@@ -17,26 +18,32 @@ The family's conventions, stated once:
 * Weight-derived operand images are cached per weight set (`cached_images`)."""
 from __future__ import annotations
 
+import weakref
 from typing import Callable, Dict, Sequence
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import edge_max, edge_rank, edge_weight, edge_window, ops
+from . import block_tail, edge_max, edge_rank, edge_weight, edge_window, ops
 
 Tensor = torch.Tensor
 
 
 # ----------------------------------------------------------------------------- operand images
 # one dictionary per builder: a layer that reaches the cap does not evict another layer's images
-_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}, "coord": {}, "bilateral": {}}
+_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}, "coord": {}, "bilateral": {}, "tail": {}}
 
 
 def cached_images(cache: Dict[tuple, tuple], weights: Sequence[Tensor], extra: tuple, build: Callable):
     """build(*detached weights), cached in `cache` until a weight changes: the key is the weights' (data_ptr, shape) and `extra`; an entry is stale
     once a weight's (ops.weights_epoch_of, torch version counter) stamp moves -- an in-place write, or an optimiser step of
-    spgan.optim.Adam, which rewrites parameters invisibly to torch and bumps the epoch of their storage (the staleness rule of nets._t).
+    spgan.optim.Adam, which rewrites parameters invisibly to torch and bumps the epoch of their storage (the staleness rule of nets._t) --
+    or once a weight it was built from has died: the allocator may hand a dead weight's address, with a fresh version counter, to the next
+    module's weight of the same shape, so every entry keeps weak references to its weights and counts a dead one as a miss.  Callers
+    therefore pass the long-lived weight objects themselves (the Parameters, as autograd hands them to forward and back from
+    ctx.saved_tensors): an entry built from a temporary -- a view, a .detach() -- dies with it and never hits.  A rebuild
+    overwrites the entry: the bookkeeping does not grow with the number of optimiser steps.
     Inside a capture the cache is neither read nor written: the images are rebuilt there, so that their kernels are part of the graph
     and every replay sees the weights of that moment.  The dictionary is cleared when it holds 64 entries."""
     ws = [w.detach() for w in weights]
@@ -45,12 +52,12 @@ def cached_images(cache: Dict[tuple, tuple], weights: Sequence[Tensor], extra: t
     key = (extra,) + tuple([(w.data_ptr(), w.shape) for w in ws])
     stamp = [(ops.weights_epoch_of(w), w._version) for w in ws]
     hit = cache.get(key)
-    if hit is not None and hit[0] == stamp:
+    if hit is not None and hit[0] == stamp and all(r() is not None for r in hit[2]):
         return hit[1]
     if len(cache) >= 64:
         cache.clear()
     img = build(*ws)
-    cache[key] = (stamp, img)
+    cache[key] = (stamp, img, [weakref.ref(w) for w in weights])
     return img
 
 
@@ -131,6 +138,16 @@ def coord_images(Wh: Tensor, Wf: Tensor, Wx: Tensor, Wa2: Tensor, Wa3: Tensor, W
         return (Wst_h, Wst_f, Wst_x, torch.cat([Wst_h, Wst_f], dim=0).t().contiguous(), Wst_x.t().contiguous(), Wm2.contiguous(), Wm2.t().contiguous(),
                 Wm3.contiguous(), Wm3.t().contiguous(), W2i, W2i.t().contiguous())
     return cached_images(_IMAGES["coord"], (Wh, Wf, Wx, Wa2, Wa3, W2), (), build)
+
+
+def tail_images(Wa: Tensor, Cs: int):
+    """add_cov's Conv1d weight [Fo, Cs + C, 1] over cat[xs broadcast, a] -> (W_s [Fo,Cs], W_e [Fo,C], W_s^T, W_e^T): the halves that meet the
+    global vector and the per-point features (BlockTailFn)"""
+    def build(Wa):
+        Wm = Wa.view(Wa.shape[0], -1)
+        Ws, We = Wm[:, :Cs].contiguous(), Wm[:, Cs:].contiguous()
+        return Ws, We, Ws.t().contiguous(), We.t().contiguous()
+    return cached_images(_IMAGES["tail"], [Wa], (Cs,), build)
 
 
 def parity_major(t: Tensor, dim: int = 0) -> Tensor:
@@ -808,3 +825,113 @@ class BilateralUpsampleEdgeConvFn(Function):
         s1 = channel_major(sums1.view(2, 4 * C), 1).reshape(-1)           # [sum g | sum g*uhat], each back in the module's channel order
         return (None, dx, dpc, dW1, db1) + gb(s1, need, 5) + (dWf, dbf) + gb(sumsf, need, 9) + (dWx, dbx) + gb(sumsx, need, 13) + \
             (dWa2, dba2) + gb(sums2, need, 17) + (dWa3, dba3) + gb(sums3, need, 21) + (dV, db2) + gb(sumsc, need, 25)
+
+
+# ----------------------------------------------------------------------------- the blocks' tail
+class PointMaxFn(Function):
+    """[B,C,N] -> [B,C]: the max over the points in front of a block's global branch (torch.max(x, 2) / MaxPool2d((1, N)) in the reference);
+    the cotangent goes to the arg-max point."""
+
+    @staticmethod
+    def forward(ctx, x):
+        B, C, N = x.shape
+        out, arg = ops.maxpool(ops.cm_to_pm(x), B, N)
+        ctx.B, ctx.N = B, N
+        ctx.save_for_backward(arg)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        arg, = ctx.saved_tensors
+        return ops.pm_to_cm(ops.scatter_rows(dout, arg, ctx.B * ctx.N), ctx.B, ctx.N)
+
+
+class _Shape:
+    def __init__(self, B, N, training):
+        self.B, self.N, self.training = B, N, training
+
+
+class BlockTailFn(Function):
+    """(x_out, g_out) of a bilateral / deform block (Generation/modules.py:928-1391) from Y [B,C,L], the channel-major output of the block's
+    edge convolution, and the global vectors xs [B,Cs], g [B,Cg] | None.  With a = lrelu(bn(Y)), the block's BatchNorm1d + LeakyReLU:
+      plain blocks:   x_out = cat[xs broadcast, a] [B,Cs+C,L], g_out = cat[g broadcast, a] [B,Cg+C,L] | None -- one pass over Y writes both
+                      (csrc/block_tail.hip); neither a nor the repeated vectors exist on their own.
+      middle blocks   (Wa, ba, ga, bea = add_cov's Conv1d(Cs+C -> Fo) and BatchNorm1d given): x_out = lrelu(bn_add(Wa cat[xs broadcast, a] + ba))
+                      [B,Fo,L] without the concatenation: Wa = [W_s | W_e], W_s xs[b] + ba enters the product as a per-shape bias, a as the
+                      operand prologue on the point-major copy of Y, bn_add's statistics come from the product's epilogue.  In backward
+                      the cotangent of a through the product is brought to channel-major once and joins g_out's inside the tail's backward
+                      (`extra`), so that the block's BatchNorm backward sees one summed cotangent; dxs and dW_s come from the per-shape
+                      column sums of the product's cotangent.
+    holder: name, training, slope, bn (the block's BatchNorm1d), bn_add (middle blocks).  An output nobody uses reaches the kernels as a
+    NULL cotangent, not as zeros.  Saved (all through save_for_backward, so that nothing of the tail outlives its backward): Y, the
+    statistics and, in the middle blocks, the point-major copy of Y and the pre-norm product Z [B*L,Fo]."""
+
+    @staticmethod
+    def forward(ctx, h, Y, xs, g, gamma, beta, Wa, ba, ga, bea):
+        B, C, L = Y.shape
+        train, middle = h.training, Wa is not None
+        st = bn_stats(h.bn, train, B * L, gamma, beta, records=block_tail.cm_stats(Y) if train else None)
+        x_out = g_out = Z = sta = Y_pm = None
+        if not middle or g is not None:
+            x_out, g_out = block_tail.block_tail_fwd(Y, None if middle else xs, g, st[0], st[1], h.slope, want_x=not middle, want_g=g is not None)
+        if middle:
+            Ws, We, _, _ = tail_images(Wa, xs.shape[1])
+            rb = ops.gemm_nt(xs, Ws, ba, exact=True)                                  # [B,Fo]: W_s xs[b] + ba
+            pro, bna = (st[0], st[1], h.slope), h.bn_add
+            Y_pm = ops.cm_to_pm(Y)                                                    # kept for the weight gradient: one transpose per step
+            if train:
+                Z, sta = ops.gemm_nt(Y_pm, We, rowbias=rb, rows_per_group=L, pro=pro, bn=(ga, bea, bna.running_mean, bna.running_var),
+                                     exact=True)
+                bna.num_batches_tracked += 1
+            else:
+                Z = ops.gemm_nt(Y_pm, We, rowbias=rb, rows_per_group=L, pro=pro, exact=True)
+                sta = ops.bn_prepare(None, None, ga, bea, B * L, False, bna.running_mean, bna.running_var, eps=float(bna.eps))
+            x_out = ops.pm_to_cm(ops.affine_act(Z, sta[0], sta[1], h.slope), B, L)
+        ctx.h, ctx.Cg = h, 0 if g is None else g.shape[1]
+        # the statistics are saved tensors, not attributes: autograd drops them with this node's backward, before the layer's backward runs
+        ctx.save_for_backward(Y, xs, gamma, Wa, ga, Z, Y_pm, st, *(sta if sta is not None else (None,) * 4))
+        return x_out, g_out
+
+    @staticmethod
+    def backward(ctx, dx_out, dg_out):
+        refuse_double_backward(ctx.h.name)
+        return BlockTailFn._backward(ctx, dx_out, dg_out)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dx_out, dg_out):
+        Y, xs, gamma, Wa, ga, Z, Y_pm, st, *sta = ctx.saved_tensors
+        h = ctx.h
+        B, C, L = Y.shape
+        train, middle, Cg = h.training, Wa is not None, ctx.Cg
+        scale, shift, invstd, mean = st
+        need = ctx.needs_input_grad
+        dout_g = None if dg_out is None else dg_out.contiguous()
+        dout_x = extra = dxs = dWa = dba = dga = dbea = None
+        if not middle:
+            Cs = xs.shape[1]
+            dout_x = None if dx_out is None else dx_out.contiguous()
+        elif dx_out is not None:
+            Cs = 0
+            _, _, Wst, Wet = tail_images(Wa, xs.shape[1])
+            dz, sums_a = lrelu_bn_bwd(dx_out, Z, sta, ga, _Shape(B, L, train), h.slope)
+            cs = ops.colsum(dz, L)                                                     # [B,Fo]: what the per-shape bias sees
+            if need[6]:
+                dWa = torch.cat([ops.gemm_tn(cs, xs, exact=True), ops.gemm_tn(dz, Y_pm, pro=(scale, shift, h.slope), exact=True)],
+                                dim=1).view_as(Wa)
+            dxs = ops.gemm_nt(cs, Wst, exact=True) if need[2] else None
+            extra = ops.pm_to_cm(ops.gemm_nt(dz, Wet, exact=True), B, L)
+            dba = dbias(dz, train) if need[7] else None
+            dga, dbea = gb(sums_a, need, 8)
+            del dz
+        else:
+            Cs = 0
+        sums, dxs_t, dg = block_tail.block_tail_bwd_reduce(Y, dout_x, dout_g, extra, Cs, Cg, scale, shift, mean, invstd, h.slope,
+                                                           want_dxs=need[2], want_dg=need[3])
+        dY = None
+        if need[1]:
+            dY = block_tail.block_tail_bwd_apply(Y, dout_x, dout_g, extra, Cs, Cg, scale, shift, mean, invstd, gamma, sums if train else None, h.slope)
+        if not middle:
+            dxs = dxs_t
+        return (None, dY, dxs if need[2] else None, dg) + gb(sums, need, 4) + (dWa, dba, dga, dbea)

@@ -999,3 +999,205 @@ class bilateral_upsample_edgeConv(nn.Module):
         out = edge_conv.BilateralUpsampleEdgeConvFn.apply(h, x.contiguous(), pc.contiguous(), *params)
         self.last_idx = h.last_idx
         return out
+
+
+# ----------------------------------------------------------------------------- the blocks of Generation/modules.py:928-1391
+def _fc(Fin, Fout):
+    return nn.Sequential(nn.Linear(Fin, Fin), nn.BatchNorm1d(Fin), nn.LeakyReLU(inplace=True),
+                         nn.Linear(Fin, Fout), nn.BatchNorm1d(Fout), nn.LeakyReLU(inplace=True))
+
+
+def _g_fc(Fout):
+    return nn.Sequential(nn.Linear(Fout, 512), nn.BatchNorm1d(512), nn.LeakyReLU(inplace=True))
+
+
+def _add_cov(Fout):
+    return nn.Sequential(nn.Conv1d(2 * Fout, Fout, 1), nn.BatchNorm1d(Fout), nn.LeakyReLU(inplace=True))
+
+
+class _Block(nn.Module):
+    """The shared body of the bilateral / deform blocks: an edge convolution, BatchNorm1d + LeakyReLU over its output, a global branch
+    (max over the points -> fc [-> g_fc], on B rows: the existing GEMM / BatchNorm launchers through pointnet_util._SharedMLPFn) and the
+    concatenation of the broadcast global vectors with the per-point features -- in the middle blocks followed by add_cov, a Conv1d + BatchNorm1d +
+    LeakyReLU over that concatenation.  Everything behind the layer is edge_conv.BlockTailFn (csrc/block_tail.hip): no repeated vector, no
+    activated copy of the layer's output and, in the middle blocks, no concatenated [B,2Fout,N] tensor exists in forward or backward.
+    The sub-modules are parameter containers with the reference's names and order: reference state_dicts load strictly both ways.
+    idx (an extension, as on the layers): the graph for the block's edge convolution.  last_idx: the graph of the latest forward.
+    Train mode needs B > 1 (BatchNorm1d over the B rows of the global branch), as in the reference.  Once differentiable."""
+    _pc = False              # forward(x, pc)
+    _two = False             # returns (x_out, g_out)
+
+    def _parts(self):
+        """-> (layer, bn, act) of the block"""
+        seq = self.upsample_cov if hasattr(self, "upsample_cov") else self.deform_cov
+        if isinstance(seq, nn.Sequential):
+            return seq[0], seq[1], seq[2]
+        return seq, self.bn_uc, self.relu_uc
+
+    @property
+    def last_idx(self) -> Optional[torch.Tensor]:
+        return self._parts()[0].last_idx
+
+    def _run(self, x, pc, idx):
+        name = type(self).__name__
+        layer, bn, act = self._parts()
+        if x.dim() != 3:
+            raise ValueError("%s: x must be [B,Fin,N], got %s" % (name, tuple(x.shape)))
+        B, _, N = x.shape
+        pool = getattr(self, "maxpool", None)
+        if pool is not None:
+            mp = pool.kernel_size[1]
+            if mp != N:
+                raise ValueError("%s: maxpool=%d must equal the number of points N=%d (the pooled [B,Fin,N-maxpool+1] tensor is viewed as the "
+                                 "[B,Fin] input of fc)" % (name, mp, N))
+        if self.training and B == 1:
+            raise ValueError("%s: train mode needs more than one shape per batch (BatchNorm1d over the B rows of the global branch), got B=1" % name)
+        g_fc, add_cov = getattr(self, "g_fc", None), getattr(self, "add_cov", None)
+        acts = [act, self.fc[2], self.fc[5]] + ([g_fc[2]] if g_fc is not None else []) + ([add_cov[2]] if add_cov is not None else [])
+        slopes = {float(a.negative_slope) for a in acts}
+        if len(slopes) != 1:
+            raise NotImplementedError("%s: the block's LeakyReLUs must share one slope, got %s" % (name, sorted(slopes)))
+        slope = slopes.pop()
+        gemm_bns = [self.fc[1], self.fc[4]] + ([g_fc[1]] if g_fc is not None else []) + ([add_cov[1]] if add_cov is not None else [])
+        for b_ in gemm_bns + [bn]:
+            if b_.momentum is None or not b_.track_running_stats:
+                raise NotImplementedError("%s: BatchNorm1d with momentum=None or track_running_stats=False is not supported" % name)
+        for b_ in gemm_bns:          # their statistics are finalised in the epilogue of the producing GEMM, with the library's constants
+            if float(b_.eps) != ops.BN_EPS or float(b_.momentum) != ops.BN_MOMENTUM:
+                raise NotImplementedError("%s: the BatchNorm1d of fc / g_fc / add_cov must keep eps=%g and momentum=%g" % (name, ops.BN_EPS, ops.BN_MOMENTUM))
+        # The global branch runs in front of the layer, as in the reference.  Autograd runs the nodes of a graph latest first, so the
+        # branch's backward then runs after the layer's, where the block's memory peaks: the dense [B,Fin,N] cotangent of the max and the
+        # gradients of fc / g_fc do not exist yet while the layer's backward holds its tensors, only the branch's saved [B,*] rows do
+        # (without g, which nothing but the tail's forward reads: keep_out=False).
+        # x is looked at here only as far as the branch's launchers need; the layer checks x (and pc, idx) and refuses a CPU tensor, and
+        # what it refuses on its own (Fin != Fout) comes first, as on the layer.
+        xs = g = None
+        if x.is_cuda and x.dtype == torch.float32 and x.shape[1] == layer.Fin:          # otherwise the layer refuses x below
+            from . import pointnet_util
+            mlp = pointnet_util._SharedMLPFn.apply
+            xs = mlp(pointnet_util._Holder(K=1, training=self.training, bns=[self.fc[1], self.fc[4]], slope=slope), edge_conv.PointMaxFn.apply(x.contiguous()),
+                     self.fc[0].weight, self.fc[0].bias, self.fc[1].weight, self.fc[1].bias, self.fc[3].weight, self.fc[3].bias, self.fc[4].weight, self.fc[4].bias)
+            if g_fc is not None:
+                g = mlp(pointnet_util._Holder(K=1, training=self.training, bns=[g_fc[1]], slope=slope, keep_out=False), xs, g_fc[0].weight, g_fc[0].bias, g_fc[1].weight, g_fc[1].bias)
+        y = layer(x, pc, idx=idx) if self._pc else layer(x, idx=idx)
+        h = _Holder(name=name, training=self.training, slope=slope, bn=bn, bn_add=None if add_cov is None else add_cov[1])
+        ac = (None, None, None, None) if add_cov is None else (add_cov[0].weight, add_cov[0].bias, add_cov[1].weight, add_cov[1].bias)
+        x_out, g_out = edge_conv.BlockTailFn.apply(h, y.contiguous(), xs, g, bn.weight, bn.bias, *ac)
+        return (x_out, g_out) if self._two else x_out
+
+
+class bilateral_block_l1(_Block):
+    """Generation/modules.py:928-973: forward(x [B,Fin,N], idx=None) -> (x_out [B,2Fout,2N], g_out [B,512+Fout,2N]) around
+    upsample_edgeConv(Fin, Fout, num_k // 2).  maxpool must equal N (ValueError otherwise; the reference fails inside fc's Linear).  See _Block."""
+    _two = True
+
+    def __init__(self, Fin, Fout, maxpool, stride=1, num_k=20):
+        super().__init__()
+        self.maxpool = nn.MaxPool2d((1, maxpool), (1, 1))
+        self.upsample_cov = nn.Sequential(upsample_edgeConv(Fin, Fout, num_k // 2, 1), nn.BatchNorm1d(Fout), nn.LeakyReLU(inplace=True))
+        self.fc = _fc(Fin, Fout)
+        self.g_fc = _g_fc(Fout)
+
+    def forward(self, x, idx: Optional[torch.Tensor] = None):
+        return self._run(x, None, idx)
+
+
+class bilateral_block_l2(_Block):
+    """Generation/modules.py:976-1020: forward(x [B,Fin,N], pc [B,3,N], idx=None) -> (x_out [B,2Fout,2N], g_out [B,512+Fout,2N]) around
+    bilateral_upsample_edgeConv(Fin, Fout, num_k // 2).  maxpool must equal N (ValueError otherwise).  See _Block."""
+    _pc = True
+    _two = True
+
+    def __init__(self, Fin, Fout, maxpool, stride=1, num_k=20, softmax=True):
+        super().__init__()
+        self.maxpool = nn.MaxPool2d((1, maxpool), (1, 1))
+        self.upsample_cov = bilateral_upsample_edgeConv(Fin, Fout, num_k // 2, 1, softmax=softmax)
+        self.bn_uc = nn.BatchNorm1d(Fout)
+        self.relu_uc = nn.LeakyReLU(inplace=True)
+        self.fc = _fc(Fin, Fout)
+        if self._two:
+            self.g_fc = _g_fc(Fout)
+
+    def forward(self, x, pc, idx: Optional[torch.Tensor] = None):
+        return self._run(x, pc, idx)
+
+
+class bilateral_block_l3(bilateral_block_l2):
+    """Generation/modules.py:1023-1069: as bilateral_block_l2."""
+
+
+class bilateral_block_l4(bilateral_block_l2):
+    """Generation/modules.py:1072-1106: bilateral_block_l2 without g_fc: forward(x, pc, idx=None) -> x_out [B,2Fout,2N]."""
+    _two = False
+
+
+class bilateral_block(_Block):
+    """Generation/modules.py:1109-1144: forward(x [B,Fin,N], idx=None) -> x_out [B,2Fout,2N] around upsample_edgeConv(Fin, Fout, num_k // 2).
+    maxpool is accepted and unused, as in the reference (the pooling is torch.max).  See _Block."""
+
+    def __init__(self, Fin, Fout, maxpool, stride=1, num_k=20):
+        super().__init__()
+        self.upsample_cov = nn.Sequential(upsample_edgeConv(Fin, Fout, num_k // 2, 1), nn.BatchNorm1d(Fout), nn.LeakyReLU(inplace=True))
+        self.fc = _fc(Fin, Fout)
+
+    def forward(self, x, idx: Optional[torch.Tensor] = None):
+        return self._run(x, None, idx)
+
+
+class deform_block_middle(_Block):
+    """Generation/modules.py:1195-1253: forward(x [B,Fin,N], pc [B,3,N], idx=None) -> (x_out [B,Fout,N], g_out [B,512+Fout,N]) around
+    deform_edgeConv(Fin, Fout, num_k), with add_cov over cat[xs, x_ec].  The constructor accepts any (Fin, Fout) so that state_dicts load;
+    the forward raises ValueError unless Fin == Fout, as the layer does.  softmax is accepted and unused, as in the reference.  See _Block."""
+    _pc = True
+    _two = True
+
+    def __init__(self, Fin, Fout, stride=1, num_k=20, softmax=True):
+        super().__init__()
+        self.deform_cov = deform_edgeConv(Fin, Fout, num_k)
+        self.add_cov = _add_cov(Fout)
+        self.bn_uc = nn.BatchNorm1d(Fout)
+        self.relu_uc = nn.LeakyReLU(inplace=True)
+        self.fc = _fc(Fin, Fout)
+        self.g_fc = _g_fc(Fout)
+
+    def forward(self, x, pc, idx: Optional[torch.Tensor] = None):
+        return self._run(x, pc, idx)
+
+
+class deform_block_tail(_Block):
+    """Generation/modules.py:1256-1290: forward(x [B,Fin,N], pc [B,3,N], idx=None) -> x_out [B,2Fout,N] around deform_edgeConv(Fin, Fout, num_k);
+    runs only with Fin == Fout (ValueError otherwise), as the layer.  softmax is accepted and unused, as in the reference.  See _Block."""
+    _pc = True
+
+    def __init__(self, Fin, Fout, stride=1, num_k=20, softmax=True):
+        super().__init__()
+        self.deform_cov = deform_edgeConv(Fin, Fout, num_k)
+        self.bn_uc = nn.BatchNorm1d(Fout)
+        self.relu_uc = nn.LeakyReLU(inplace=True)
+        self.fc = _fc(Fin, Fout)
+
+    def forward(self, x, pc, idx: Optional[torch.Tensor] = None):
+        return self._run(x, pc, idx)
+
+
+class deform_block_feat_middle(_Block):
+    """Generation/modules.py:1293-1337: forward(x [B,Fin,N], idx=None) -> x_out [B,Fout,N] around deform_edgeConv_feat(Fin, Fout, num_k,
+    softmax), with add_cov over cat[xs, x_ec].  See _Block."""
+
+    def __init__(self, Fin, Fout, stride=1, num_k=20, softmax=True):
+        super().__init__()
+        self.deform_cov = deform_edgeConv_feat(Fin, Fout, num_k, softmax=softmax)
+        self.add_cov = _add_cov(Fout)
+        self.bn_uc = nn.BatchNorm1d(Fout)
+        self.relu_uc = nn.LeakyReLU(inplace=True)
+        self.fc = _fc(Fin, Fout)
+        if self._two:
+            self.g_fc = _g_fc(Fout)
+
+    def forward(self, x, idx: Optional[torch.Tensor] = None):
+        return self._run(x, None, idx)
+
+
+class deform_block_feat(deform_block_feat_middle):
+    """Generation/modules.py:1339-1391: deform_block_feat_middle with g_fc: forward(x, idx=None) -> (x_out [B,Fout,N], g_out [B,512+Fout,N])."""
+    _two = True

@@ -370,12 +370,14 @@ class _Holder:
 
 class _SharedMLPFn(torch.autograd.Function):
     """rows a0 [Q*K, Cin] -> [Q, Cout]: (1x1 conv -> BatchNorm -> ReLU) per layer, then max over the K consecutive rows of a group
-    (K = 1: the per-row activations).  inputs: holder(K, training, bns = the nn.BatchNorm modules), a0, then (weight, bias, gamma, beta)
-    per layer."""
+    (K = 1: the per-row activations).  inputs: holder(K, training, bns = the nn.BatchNorm modules[, slope: LeakyReLU(slope) instead of
+    the ReLU][, keep_out=False (K = 1 only): the result is not saved but formed again in backward from the last pre-norm product, for a
+    caller whose result would otherwise live only through this node]), a0, then (weight, bias, gamma, beta) per layer."""
 
     @staticmethod
     def forward(ctx, holder, a0, *params):
         K, training = holder.K, holder.training
+        slope = float(getattr(holder, "slope", RELU))
         M = a0.shape[0]
         Q = M // K
         ys, bns = [], []
@@ -390,24 +392,29 @@ class _SharedMLPFn(torch.autograd.Function):
                 y = ops.gemm_nt(a, W2, b, pro=pro)
                 st = ops.bn_prepare(None, None, gamma, beta, M, False, bn.running_mean, bn.running_var)
             ys.append(y); bns.append(st)
-            a, pro = y, (st[0], st[1], RELU)
+            a, pro = y, (st[0], st[1], slope)
         sc, sh = bns[-1][0], bns[-1][1]
         if K == 1:
-            out, arg = ops.affine_act(ys[-1], sc, sh, RELU), None
+            out, arg = ops.affine_act(ys[-1], sc, sh, slope), None
         else:
-            out, arg = _group_max(ys[-1], Q, K, sc, sh, RELU)
-        ctx.K, ctx.training, ctx.ys, ctx.bns, ctx.arg = K, training, ys, bns, arg
-        ctx.save_for_backward(a0, out, *params)
+            out, arg = _group_max(ys[-1], Q, K, sc, sh, slope)
+        ctx.K, ctx.training, ctx.slope, ctx.L = K, training, slope, len(ys)
+        keep_out = K > 1 or getattr(holder, "keep_out", True)
+        # the pre-norm products and the statistics are saved tensors, not attributes: autograd drops them with this node's backward
+        ctx.save_for_backward(a0, out if keep_out else None, arg, *params, *ys, *[t for st in bns for t in st])
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        a0, out, *params = ctx.saved_tensors
-        K, ys, bns = ctx.K, ctx.ys, ctx.bns
+        a0, out, arg, *rest = ctx.saved_tensors
+        K, slope, L = ctx.K, ctx.slope, ctx.L
+        params, ys, flat = rest[:4 * L], rest[4 * L:5 * L], rest[5 * L:]
+        bns = [flat[4 * li:4 * li + 4] for li in range(L)]
         M = a0.shape[0]
-        L = len(ys)
         grads = [None] * len(params)
-        g, sums = _group_max_bwd(dout.contiguous(), out, ctx.arg, ys[-1], bns[-1][3], bns[-1][2], RELU, K)
+        if out is None:
+            out = ops.affine_act(ys[-1], bns[-1][0], bns[-1][1], slope)
+        g, sums = _group_max_bwd(dout.contiguous(), out, arg, ys[-1], bns[-1][3], bns[-1][2], slope, K)
         da0 = None
         for li in range(L - 1, -1, -1):
             W, b, gamma, beta = [p.detach() for p in params[4 * li:4 * li + 4]]
@@ -423,8 +430,8 @@ class _SharedMLPFn(torch.autograd.Function):
                 grads[4 * li + 1] = ops.colsum(dy)[0]
             if li > 0:
                 psc, psh, pinv, pmu = bns[li - 1]
-                grads[4 * li] = ops.gemm_tn(dy, ys[li - 1], pro=(psc, psh, RELU)).view_as(W)
-                g, s0, s1 = ops.gemm_nt_bnbwd(dy, W2.t().contiguous(), ys[li - 1], psc, psh, pmu, pinv, RELU)
+                grads[4 * li] = ops.gemm_tn(dy, ys[li - 1], pro=(psc, psh, slope)).view_as(W)
+                g, s0, s1 = ops.gemm_nt_bnbwd(dy, W2.t().contiguous(), ys[li - 1], psc, psh, pmu, pinv, slope)
                 sums = torch.cat([s0, s1])
             else:
                 grads[0] = ops.gemm_tn(dy, a0).view_as(W)
