@@ -1089,6 +1089,40 @@ size_t spgan_scale_residual_bwd_ws_bytes(size_t n);
 int spgan_scale_residual_bwd(const float* dy, const float* o, const float* gamma, float* d_o, float* dgamma, void* ws, size_t ws_bytes,
                              size_t n, spgan_stream_t s);
 
+/* ------------------------------------------------------------------------------------------
+ * PointTransformerLayer (Generation/modules.py:1602-1644): all-pairs vector attention without a per-pair vector in memory
+ * (DESIGN 25).  With r_ij = relu(W_p1 (pos_i - pos_j) + b_p1), Wc = W_a1 W_p2 and c = W_a1 b_p2 + b_a1:
+ *   sim_ij = w_a2 . relu(QaC_i - Ka_j + Wc r_ij),  a = softmax_j(sim),  Sv_i = sum_j a_ij v_j,  R_i = sum_j a_ij r_ij.
+ * Operands are padded images: Mp = spgan_pair_attn_padded_m(dim * mult), a multiple of 128 up to 4096, Hp = spgan_pair_attn_padded_h(H) in
+ * {32, 64} (0 = outside the domain), all padding zero.  pos [b,n,3]; Wp1p [Hp,4] = (W_p1 | b_p1); QaC = q W_a1^T + c and
+ * Ka = k W_a1^T [b*n,Mp]; Wc [Mp,Hp]; WcT [Hp,Mp]; wa2 [Mp]; v [b*n,D] with row stride ldv; D <= spgan_pair_attn_max_dim().
+ * Exact fp32 MFMA; every sum has a fixed order (no float atomics).
+ * ---------------------------------------------------------------------------------------- */
+int spgan_pair_attn_padded_m(int M);
+int spgan_pair_attn_padded_h(int H);
+int spgan_pair_attn_max_dim(void);
+/* lse_in == NULL: the forward.  Online softmax over key tiles -> Sv [b*n,D], R [b*n,Hp], lse_out [b*n] (log-sum-exp of sim; b_a2
+ * cancels and is left out).  lse_in != NULL: the backward's recomputation, P [b,n,n] = exp(sim - lse_in); v, Sv, R, lse_out unused. */
+int spgan_pair_attn_fwd(const float* pos, const float* Wp1p, const float* QaC, const float* Ka, const float* Wc, const float* wa2,
+                        const float* v, int ldv, int b, int n, int D, int Mp, int Hp, const float* lse_in, float* Sv, float* R,
+                        float* lse_out, float* P, spgan_stream_t s);
+/* dS [b,n,n] holds dout_i . v_j on entry (a per-cloud GEMM of the caller) and on return P_ij (g_ij - delta_i),
+ * g_ij = dout_i . v_j + dR_i . r_ij, delta_i = sum_j P_ij g_ij / sum_j P_ij (= dout_i . (out_i - b_p2), from the numbers it is
+ * subtracted from); dR = dout W_p2 [b*n,Hp] */
+int spgan_pair_attn_dsim(const float* P, const float* dR, const float* pos, const float* Wp1p, int b, int n, int Hp, float* dS,
+                         spgan_stream_t s);
+/* The pair backward recomputes pre_ij; dpre_ij = dS_ij w_a2 [pre_ij > 0], dz_ij = [r_ij > 0] (Wc^T dpre_ij + P_ij dR_i).
+ * role 0 (query-stationary): dA [b*n,Mp] = dQa_i = sum_j dpre_ij, Z [b*n,Hp] = sum_j dz_ij, and per workgroup one record of
+ *   ws: [records][Mp*Hp + Mp] = partial dWc (row-major [Mp,Hp]) then partial dw_a2; the caller sums the records in ascending order.
+ *   records = spgan_pair_attn_bwd_records(b, n) = b * min(n, max(1, 512 / b)): at most 512 for b <= 512, b beyond (128 KB per record
+ *   at the default Mp 512, Hp 64; 1 MB at the largest Mp 4096).
+ * role 1 (key-stationary): dA = dKa_j = -sum_i dpre_ij, Z = sum_i dz_ij; ws unused. */
+int spgan_pair_attn_bwd_records(int b, int n);
+size_t spgan_pair_attn_bwd_ws_bytes(int b, int n, int Mp, int Hp);
+int spgan_pair_attn_bwd(int role, const float* pos, const float* Wp1p, const float* QaC, const float* Ka, const float* Wc,
+                        const float* WcT, const float* wa2, const float* P, const float* dS, const float* dR, int b, int n, int Mp,
+                        int Hp, float* dA, float* Z, void* ws, size_t ws_bytes, spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

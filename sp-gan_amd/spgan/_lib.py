@@ -361,6 +361,14 @@ SIGNATURES = {
     "spgan_adam_ema_step_dev": (I, [P, P, P, P, P, SZ, F, F, F, F, P, F, I, C.c_double, I, P]),
     "spgan_adam_ema_step": (I, [P, P, P, P, P, SZ, F, F, F, F, I, F, C.c_double, I, P]),
     "spgan_ema_update_dev": (I, [P, P, SZ, C.c_double, I, P, P]),
+    "spgan_pair_attn_padded_m": (I, [I]),
+    "spgan_pair_attn_padded_h": (I, [I]),
+    "spgan_pair_attn_max_dim": (I, []),
+    "spgan_pair_attn_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, P]),
+    "spgan_pair_attn_dsim": (I, [P, P, P, P, I, I, I, P, P]),
+    "spgan_pair_attn_bwd_records": (I, [I, I]),
+    "spgan_pair_attn_bwd_ws_bytes": (SZ, [I, I, I, I]),
+    "spgan_pair_attn_bwd": (I, [I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, SZ, P]),
 }
 
 _lib = None

@@ -1201,3 +1201,36 @@ class deform_block_feat_middle(_Block):
 class deform_block_feat(deform_block_feat_middle):
     """Generation/modules.py:1339-1391: deform_block_feat_middle with g_fc: forward(x, idx=None) -> (x_out [B,Fout,N], g_out [B,512+Fout,N])."""
     _two = True
+
+
+class PointTransformerLayer(nn.Module):
+    """Generation/modules.py:1602-1644: forward(x [b,n,dim], pos [b,n,3]) -> [b,n,dim], point-major.  Pairwise vector attention:
+    a = softmax_j(attn_mlp(q_i - k_j + pos_mlp(pos_i - pos_j))), out_i = sum_j a_ij (v_j + pos_mlp(pos_i - pos_j)), computed by
+    pair_attn.PairAttnFn without any per-pair vector in memory, so that n is bounded by time and not by [b,n,n,dim] tensors.
+    Sub-modules carry the reference's names in its order (to_qkv, pos_mlp.0/2, attn_mlp.0/2): state_dicts load strictly both ways.
+    Domain (ValueError otherwise): dim <= 512, pos_mlp_hidden_dim <= 64, dim * attn_mlp_hidden_mult <= 4096.  Differentiable once in
+    x, pos and every parameter (attn_mlp.2.bias cancels in the softmax: its gradient is exactly zero)."""
+
+    def __init__(self, dim, pos_mlp_hidden_dim=64, attn_mlp_hidden_mult=4):
+        super().__init__()
+        from . import pair_attn
+        pair_attn.padded_sizes(int(dim), int(pos_mlp_hidden_dim), int(attn_mlp_hidden_mult))
+        self.dim = int(dim)
+        self.to_qkv = nn.Linear(dim, dim * 3, bias=False)
+        self.pos_mlp = nn.Sequential(nn.Linear(3, pos_mlp_hidden_dim), nn.ReLU(), nn.Linear(pos_mlp_hidden_dim, dim))
+        self.attn_mlp = nn.Sequential(nn.Linear(dim, dim * attn_mlp_hidden_mult), nn.ReLU(), nn.Linear(dim * attn_mlp_hidden_mult, 1))
+
+    def forward(self, x, pos):
+        from . import pair_attn
+        _require_gpu(x, "PointTransformerLayer")
+        _require_gpu(pos, "PointTransformerLayer")
+        if x.dim() != 3 or x.shape[2] != self.dim or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError("PointTransformerLayer(dim=%d): x must be [b,n,%d], got %s" % (self.dim, self.dim, tuple(x.shape)))
+        if tuple(pos.shape) != (x.shape[0], x.shape[1], 3):
+            raise ValueError("PointTransformerLayer: pos must be [b,n,3] = %s for x %s, got %s"
+                             % ((x.shape[0], x.shape[1], 3), tuple(x.shape), tuple(pos.shape)))
+        if x.dtype != torch.float32 or pos.dtype != torch.float32:
+            raise TypeError("PointTransformerLayer: x and pos must be float32, got %s and %s" % (x.dtype, pos.dtype))
+        p0, p2, a0, a2 = self.pos_mlp[0], self.pos_mlp[2], self.attn_mlp[0], self.attn_mlp[2]
+        return pair_attn.point_transformer(x, pos, self.to_qkv.weight, p0.weight, p0.bias, p2.weight, p2.bias, a0.weight, a0.bias,
+                                           a2.weight, a2.bias)

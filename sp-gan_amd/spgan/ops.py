@@ -477,9 +477,10 @@ def _batched3d(t: Tensor, name: str) -> Tensor:
     return t
 
 
-def gemm_nt_batched(A: Tensor, W: Tensor, out: Optional[Tensor] = None) -> Tensor:
+def gemm_nt_batched(A: Tensor, W: Tensor, out: Optional[Tensor] = None, exact: bool = False) -> Tensor:
     """Y[z] = A[z] @ W[z]^T for z < batch in ONE launch: A [Z,M,K], W [Z,N,K] -> [Z,M,N].  Row and batch strides are free
-    (column slices of wider buffers, or stride 0 to share an operand); `out` may be such a view too."""
+    (column slices of wider buffers, or stride 0 to share an operand); `out` may be such a view too.  exact=True keeps fp32 operands
+    whatever set_mfma_operands selected (as gemm_nt's)."""
     _batched3d(A, "A"); _batched3d(W, "W")
     Z, M_, K = A.shape
     if W.shape[0] != Z or W.shape[2] != K:
@@ -489,7 +490,7 @@ def gemm_nt_batched(A: Tensor, W: Tensor, out: Optional[Tensor] = None) -> Tenso
         out = torch.empty((Z, M_, N), dtype=torch.float32, device=A.device)
     elif tuple(_batched3d(out, "out").shape) != (Z, M_, N):
         raise ValueError("out must be [%d,%d,%d], got %s" % (Z, M_, N, tuple(out.shape)))
-    a = GemmNTArgs(); a.mfma_f16 = _MFMA_F16[0]; a.tile_hint = _NT_TILE_HINT[0]
+    a = GemmNTArgs(); a.mfma_f16 = 0 if exact else _MFMA_F16[0]; a.tile_hint = _NT_TILE_HINT[0]
     a.A = _p(A); a.lda = A.stride(1); a.W = _p(W); a.ldw = W.stride(1); a.Y = _p(out); a.ldy = out.stride(1)
     a.M, a.N, a.K = M_, N, K
     a.a_mode = A_PLAIN; a.epi_mode = EPI_LINEAR; a.act = ACT_NONE
