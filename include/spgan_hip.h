@@ -86,7 +86,7 @@ int spgan_concat2(const float* a, int Ca, const float* b, int Cb, int M, float* 
  * ---------------------------------------------------------------------------------------- */
 
 enum { SPGAN_A_PLAIN = 0, SPGAN_A_AFFINE_LRELU = 1, SPGAN_A_EDGE = 2 };
-enum { SPGAN_EPI_LINEAR = 0, SPGAN_EPI_MASK_OUT = 1, SPGAN_EPI_BNBWD = 2, SPGAN_EPI_EDGE_BNBWD = 3 };
+enum { SPGAN_EPI_LINEAR = 0, SPGAN_EPI_MASK_OUT = 1, SPGAN_EPI_BNBWD = 2, SPGAN_EPI_EDGE_BNBWD = 3, SPGAN_EPI_ADAIN = 4 };
 enum { SPGAN_ACT_NONE = 0, SPGAN_ACT_LRELU = 1, SPGAN_ACT_TANH = 2 };
 
 /* Column tail of the M <= 64 product kernel (the per-shape linears: one workgroup owns its columns entirely, so what would be a
@@ -186,6 +186,18 @@ typedef struct spgan_gemm_nt_args {
    * the stored tile is gout_add[m, :] + gout_scale[:] * g[m, :] (the statistics stay those of g), as spgan_gemm_dual_args.gout_add: phase B of
    * the double backward hands X = xbarA + gamma*g to the next BatchNorm backward. */
   const float* gout_add; int ld_gout_add; const float* gout_scale;
+  /* EPI_ADAIN (a_mode PLAIN, fp32 operands, N = 2C with C % 32 == 0, W = the style layer's [2C, K] weight = [gamma rows | beta rows],
+   * bias [2C] or NULL; aligned operands: K, lda, ldw multiples of 4, A and W 16-byte aligned): AdaptivePointNorm applied in the epilogue,
+   *   gamma = acc[m, c] + bias[c];  beta = acc[m, C + c] + bias[C + c];  b = m / ad_rows
+   *   xhat = (lrelu(x[b, m - b*ad_rows, c], ad_slope) - ad_mean[b, c]) * rsqrtf(ad_var[b, c] + ad_eps);  Y[m, c] = fmaf(gamma, xhat, beta)
+   * Y is [M, C] (ldy >= C); [M, 2C] is never stored.  x: row stride ad_ldx, shape b starts at ad_x + b * ad_x_shape_stride (0: every shape
+   * reads the same [ad_rows, C] block); M % ad_rows == 0; ad_mean / ad_var [M / ad_rows, C].
+   * ad_gamma != NULL: gamma alone is stored for the rows m >= ad_gamma_row0, ad_gamma[(m - ad_gamma_row0) * ad_ld_gamma + c].
+   * pool_val / pool_arg != NULL (ad_rows % 128 == 0): per 128-row tile (max, min) / (arg-max, arg-min) records [M/128, C, 2] of Y, in the
+   * format of the LINEAR epilogue's records (first row on ties), for spgan_pool_finalize*. */
+  const float* ad_x; int ad_ldx; long ad_x_shape_stride; int ad_rows;
+  const float* ad_mean; const float* ad_var; float ad_eps, ad_slope;
+  float* ad_gamma; int ad_ld_gamma, ad_gamma_row0;
 } spgan_gemm_nt_args;
 /* 1 when spgan_gemm_nt will honour y_bf16 for this problem (it runs on the 256 x 256-tile kernel with fp16 operands) */
 int spgan_gemm_nt_y16_ok(const spgan_gemm_nt_args* a);
@@ -536,11 +548,15 @@ int spgan_edge_scatter(const float* g1, const float* gy, const float* PQR, int l
  * ---------------------------------------------------------------------------------------- */
 int spgan_adain_fwd(const float* x, int M, int C, int N, float slope, const float* imean, const float* ivar, float eps,
                     const float* gb, float* out, spgan_stream_t s);
-/* dgb = [dout*xhat | dout]; partials [(M/N)*ceil(N/128)][C][2] = (sum dxh, sum dxh*xhat), dxh = dout*gamma (finalize mode 1) */
+/* dgb = [dout*xhat | dout]; partials [(M/N)*ceil(N/128)][C][2] = (sum dxh, sum dxh*xhat), dxh = dout*gamma (finalize mode 1).
+ * gamma[m, c] = gb[m * ld_gamma + c]: ld_gamma = 2C for the [M,2C] style tensor [gamma|beta], C for the gamma-only tensor the
+ * SPGAN_EPI_ADAIN epilogue stores.  Shape b's rows of x start at x + b * x_shape_stride (N*C: a dense [M,C] tensor; 0: all shapes share
+ * one [N,C] block). */
 int spgan_adain_bwd1(const float* dout, const float* x, int M, int C, int N, float slope, const float* imean, const float* ivar,
-                     float eps, const float* gb, float* dgb, float* partials, spgan_stream_t s);
+                     float eps, const float* gb, int ld_gamma, long x_shape_stride, float* dgb, float* partials, spgan_stream_t s);
 int spgan_adain_bwd2(const float* dout, const float* x, int M, int C, int N, float slope, const float* imean, const float* ivar,
-                     float eps, const float* gb, const float* S0, const float* S1, float* dx, spgan_stream_t s);
+                     float eps, const float* gb, int ld_gamma, long x_shape_stride, const float* S0, const float* S1, float* dx,
+                     spgan_stream_t s);
 
 /* ------------------------------------------------------------------------------------------
  * Backward through [BatchNorm1d -> LeakyReLU -> global max over N] (Discriminator.py:77-81,104): the incoming

@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "adain_epi.hpp"
 #include "gemm_wide.hpp"
 #include "gemm_tn_wide3.hpp"
 #include "sparse_rows.hpp"
@@ -285,7 +286,15 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_kernel(const spgan_gemm_nt_arg
     if (AMODE == A_AFFINE2) offC[i] = (unsigned)m * (unsigned)p.lda2;
   }
 #pragma unroll
-  for (int i = 0; i < BSLOT; ++i) offW[i] = (unsigned)min(n0 + lrow + 32 * i, p.N - 1) * (unsigned)p.ldw;
+  for (int i = 0; i < BSLOT; ++i) {
+    if (EPI == SPGAN_EPI_ADAIN) {
+      // staging row 64*q + 32*t + r of the weight tile (wave q's column tile t = 0 / 1, column r; slot i = 2*q + t, r = lrow) reads row
+      // t*C + n0/2 + 32*q + r of W = [gamma rows | beta rows] (C = N/2): gamma and beta of one channel meet in one lane (adain_epi.hpp)
+      const int Cn = p.N >> 1;
+      offW[i] = (unsigned)((i & 1) * Cn + min((n0 >> 1) + (i >> 1) * 32 + lrow, Cn - 1)) * (unsigned)p.ldw;
+    } else
+    offW[i] = (unsigned)min(n0 + lrow + 32 * i, p.N - 1) * (unsigned)p.ldw;
+  }
 
   // Sparse addend of the A operand (sp_val/sp_arg, one hit per (shape, column)).  Fast form: when every row of this
   // tile lies in ONE shape and the loads are 16-byte aligned, each thread fetches the (arg, val) quads of its 4 staging
@@ -580,7 +589,38 @@ __global__ __launch_bounds__(256, 3) void gemm_nt_kernel(const spgan_gemm_nt_arg
   const bool full = (rows_valid == BM) && (n0 + BN <= p.N);
 #define ROFF(r) (((r) & 3) + 8 * ((r) >> 2))
 
-  if (EPI == SPGAN_EPI_LINEAR) {
+  if constexpr (EPI == SPGAN_EPI_ADAIN && TJ == 2) {
+    // AdaptivePointNorm on the accumulators: column tile 0 of the wave holds gamma, tile 1 beta of channel c (see offW above)
+    const int Cn = p.N >> 1;
+    const int c = (n0 >> 1) + wn * 32 + l31;
+    if (full) adain_wave_epilogue<TI, false>(p, pY, acc, m0 + wm * TI * 32, lh, c);
+    else adain_wave_epilogue<TI, true>(p, pY, acc, m0 + wm * TI * 32, lh, c);
+    if (p.pool_val) {   // host: M % 128 == 0 and ad_rows % 128 == 0 -- whole row tiles, each inside one shape; records as the LINEAR epilogue's
+      constexpr int WGM = G::WGM;
+      float* pvx = pool;
+      int* pax = reinterpret_cast<int*>(pool + WGM * BN);
+      float* pvn = pool + 2 * WGM * BN;
+      int* pan = reinterpret_cast<int*>(pool + 3 * WGM * BN);
+      float vx, vn;
+      int ax, an;
+      adain_wave_extrema<TI>(acc, rbase, vx, ax, vn, an);
+      const int q = wm * BN + wn * 32 + l31;
+      if (lh == 0) { pvx[q] = vx; pax[q] = ax; pvn[q] = vn; pan[q] = an; }
+      __syncthreads();
+      if (wm == 0 && lh == 0 && c < Cn) {
+        const int q0 = wn * 32 + l31;
+        vx = pvx[q0]; vn = pvn[q0]; ax = pax[q0]; an = pan[q0];
+#pragma unroll
+        for (int w = 1; w < WGM; ++w) {  // wave w holds higher rows than wave w-1: strict compares keep the first
+          if (pvx[w * BN + q0] > vx) { vx = pvx[w * BN + q0]; ax = pax[w * BN + q0]; }
+          if (pvn[w * BN + q0] < vn) { vn = pvn[w * BN + q0]; an = pan[w * BN + q0]; }
+        }
+        const size_t o = ((size_t)t.tm * Cn + c) * 2;
+        p.pool_val[o] = vx; p.pool_val[o + 1] = vn;
+        p.pool_arg[o] = ax; p.pool_arg[o + 1] = an;
+      }
+    }
+  } else if (EPI == SPGAN_EPI_LINEAR) {
     float csum[TJ];
     // per-group bias rows: usable on the straight-line path when the whole tile lies in one group (per-shape bias, N % 128 == 0) or
     // when the "group" is a single row (a dense [M,N] addend)
@@ -2091,8 +2131,8 @@ extern "C" int spgan_gemm_nt(const spgan_gemm_nt_args* a, spgan_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
   SPGAN_CHECK_ARG(a && a->A && a->W && a->M > 0 && a->N > 0 && a->K > 0);
   SPGAN_CHECK_ARG(a->Y || (a->pool_val && a->epi_mode == SPGAN_EPI_LINEAR));
-  if (a->pool_val) SPGAN_CHECK_ARG(a->pool_arg && a->epi_mode == SPGAN_EPI_LINEAR && a->M > 64);
-  SPGAN_CHECK_ARG(a->lda >= a->K && a->ldw >= a->K && a->ldy >= a->N);
+  if (a->pool_val) SPGAN_CHECK_ARG(a->pool_arg && (a->epi_mode == SPGAN_EPI_LINEAR || a->epi_mode == SPGAN_EPI_ADAIN) && a->M > 64);
+  SPGAN_CHECK_ARG(a->lda >= a->K && a->ldw >= a->K && a->ldy >= (a->epi_mode == SPGAN_EPI_ADAIN ? a->N / 2 : a->N));
   SPGAN_CHECK_ARG((uint64_t)a->M * (uint64_t)a->lda < (1ull << 32) && (uint64_t)a->N * (uint64_t)a->ldw < (1ull << 32));  // 32-bit operand offsets
   if (a->a_mode != SPGAN_A_PLAIN) SPGAN_CHECK_ARG(a->p_scale && a->p_shift);
   if (a->p_group_rows != 0)  // row groups (per-group prologue vectors when there is a prologue): whole 128-row tiles per group, not for the M <= 64 kernel
@@ -2146,6 +2186,21 @@ extern "C" int spgan_gemm_nt(const spgan_gemm_nt_args* a, spgan_stream_t s_) {
                       a->e_idx && a->e_k > 0 && a->e_bias2);
       if (a->A2) return launch_nt<A_AFFINE2, SPGAN_EPI_EDGE_BNBWD>(*a, s);
       return launch_nt<SPGAN_A_PLAIN, SPGAN_EPI_EDGE_BNBWD>(*a, s);
+    case SPGAN_EPI_ADAIN: {
+      // the style GEMM of an AdaptivePointNorm layer with the normalisation in its epilogue (spgan_hip.h); the kernel is chosen as for the
+      // plain product of the same sizes (256 x 256 tiles or the 128-row kernel), whose k-order per output element both share
+      const int Cn = a->N / 2;
+      SPGAN_CHECK_ARG(a->a_mode == SPGAN_A_PLAIN && a->mfma_f16 == 0 && a->batch <= 1 && !a->tail.enabled && !a->rowbias && !a->stats && !a->A2 &&
+                      !a->sp_val && !a->a_half && !a->y_bf16 && !a->y_half && a->act == SPGAN_ACT_NONE && a->M > 64);
+      SPGAN_CHECK_ARG(a->N % 64 == 0 && a->K % 4 == 0 && a->lda % 4 == 0 && a->ldw % 4 == 0 && al16(a->A) && al16(a->W));
+      SPGAN_CHECK_ARG(a->ad_x && a->ad_mean && a->ad_var && a->ad_rows > 0 && a->M % a->ad_rows == 0 && a->ad_ldx >= Cn && a->ad_x_shape_stride >= 0);
+      SPGAN_CHECK_ARG((uint64_t)a->M * (uint64_t)a->ldy < (1ull << 32) && (uint64_t)a->ad_rows * (uint64_t)a->ad_ldx < (1ull << 32));
+      if (a->ad_gamma) SPGAN_CHECK_ARG(a->ad_ld_gamma >= Cn && a->ad_gamma_row0 >= 0 && a->ad_gamma_row0 < a->M && (uint64_t)a->M * (uint64_t)a->ad_ld_gamma < (1ull << 32));
+      if (a->pool_val) SPGAN_CHECK_ARG(a->ad_rows % BM == 0);   // a record tile never straddles two shapes
+      if (spgan_nt_wide_selected(*a)) return spgan_launch_nt_wide(*a, s);
+      launch_nt_cfg<SPGAN_A_PLAIN, SPGAN_EPI_ADAIN, 0, 1, 1>(*a, s);
+      return spgan_launch_status();
+    }
     default:
       return SPGAN_EINVAL;
   }

@@ -76,7 +76,10 @@ __global__ __launch_bounds__(WTHREADS, 2) void gemm_nt_wide_kernel(const spgan_g
   const int lrow = tid >> 3, lc4 = (tid & 7) * 4;
   // 32-bit element offsets (host: M*lda, N*ldw < 2^32): scalar base + 32-bit offset addressing
   const unsigned oa = (unsigned)(m0 + lrow) * (unsigned)p.lda + (unsigned)lc4, sa = (unsigned)RPP * (unsigned)p.lda;
-  const unsigned ow = (unsigned)(n0 + lrow) * (unsigned)p.ldw + (unsigned)lc4, sw = (unsigned)RPP * (unsigned)p.ldw;
+  // EPI_ADAIN: staging row 64*q + 32*t + r of the weight tile (wave q's column tile t = 0 / 1, column r) reads row t*C + n0/2 + 32*q + r
+  // of W = [gamma rows | beta rows] (C = N/2): gamma and beta of one channel meet in one lane (adain_epi.hpp); W itself is not rearranged
+  const unsigned wrow = EPI == SPGAN_EPI_ADAIN ? (unsigned)((lrow >> 5) * (p.N >> 1) + (n0 >> 1) + (lrow & 31)) : (unsigned)(n0 + lrow);
+  const unsigned ow = wrow * (unsigned)p.ldw + (unsigned)lc4, sw = (unsigned)(EPI == SPGAN_EPI_ADAIN ? 32 : RPP) * (unsigned)p.ldw;
   const int sp_b = sparse ? m0 / p.sp_rows : 0;  // the whole tile lies in one shape (host: sp_rows % 256 == 0)
   // prologue vectors: one pair for all rows, or one pair per group of p_group_rows rows (host: p_group_rows % 256 == 0)
   const float* pPsc = p_.p_scale;
@@ -223,6 +226,7 @@ int launch_epi(const spgan_gemm_nt_args& a, hipStream_t s) {
     case SPGAN_EPI_LINEAR: return launch<AMODE, SPGAN_EPI_LINEAR>(a, s);
     case SPGAN_EPI_MASK_OUT: return AMODE == SPGAN_A_PLAIN ? launch<SPGAN_A_PLAIN, SPGAN_EPI_MASK_OUT>(a, s) : SPGAN_EINVAL;
     case SPGAN_EPI_BNBWD: return launch<AMODE, SPGAN_EPI_BNBWD>(a, s);
+    case SPGAN_EPI_ADAIN: return (AMODE == SPGAN_A_PLAIN && a.mfma_f16 == 0) ? launch_op<SPGAN_A_PLAIN, SPGAN_EPI_ADAIN, 0>(a, s) : SPGAN_EINVAL;
   }
   return SPGAN_EINVAL;
 }
@@ -242,6 +246,7 @@ bool spgan_nt_wide_eligible(const spgan_gemm_nt_args& a) {
   if (a.sp_val) {
     if (a.a_mode != SPGAN_A_AFFINE_LRELU || a.sp_rows % WM || !al16(a.sp_val) || !al16(a.sp_arg)) return false;
   }
+  if (a.epi_mode == SPGAN_EPI_ADAIN) return a.a_mode == SPGAN_A_PLAIN && a.mfma_f16 == 0 && !a.rowbias && !a.stats;   // fp32 operands only
   if (a.epi_mode == SPGAN_EPI_LINEAR) {
     if (a.rowbias && a.rows_per_group != 1 && a.rows_per_group % WM) return false;
     if (!a.Y && !a.stats && !a.pool_val) return false;
@@ -262,7 +267,7 @@ bool spgan_nt_wide_pays(const spgan_gemm_nt_args& a) {
   // would run as separate calls -- the two kernels sum in different orders, and the grouped form is specified as bit-identical
   const long tiles = (long)((a.p_group_rows > 0 ? a.p_group_rows : a.M) / WM) * (a.N / WN);
   if (tiles < 256 || a.K < 128) return false;
-  return a.epi_mode == SPGAN_EPI_LINEAR || tiles >= 512;
+  return a.epi_mode == SPGAN_EPI_LINEAR || a.epi_mode == SPGAN_EPI_ADAIN || tiles >= 512;   // (ADAIN: the kernel its plain style GEMM would run)
 }
 
 bool spgan_nt_wide_selected(const spgan_gemm_nt_args& a) {

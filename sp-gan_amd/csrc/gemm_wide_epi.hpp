@@ -4,8 +4,7 @@
 // One body for every operand mode: the bits of an output depend on the accumulators only.
 #pragma once
 #include "common.hpp"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "adain_epi.hpp"
 
 // internal epilogue id (template argument only, never in spgan_gemm_nt_args.epi_mode): BNBWD whose stored tile is gout_add + gout_scale * g.
 // Its own instantiation (gemm_wide3.hip), so that the BNBWD kernels keep their registers.
@@ -143,6 +142,21 @@ __device__ __forceinline__ void wide_epilogue(const spgan_gemm_nt_args& p, f32x1
 #pragma unroll
         for (int r = 0; r < 16; ++r) yb[(size_t)((unsigned)(i * 32 + ROFF(r)) * ldy + (unsigned)(j * 32))] = acc[i][j][r] * lrelu_mask(rv[r], sl);
       }
+  } else if constexpr (EPI == SPGAN_EPI_ADAIN) {
+    // the weight tile was staged with gamma rows in the wave's column tile 0 and beta rows in tile 1 (gemm_wide.hip): channel c of both
+    static_assert(TJ == 2, "gamma / beta pairing needs the two column tiles of a wave");
+    const int c = (n0 >> 1) + wn * 32 + l31;
+    adain_wave_epilogue<TI, false>(p, p.Y, acc, m0 + wm * (TI * 32), lh, c);
+    if (p.pool_val) {   // host: ad_rows % 128 == 0, so that the wave's record tile lies in one shape
+      float vx, vn;
+      int ax, an;
+      adain_wave_extrema<TI>(acc, rbase, vx, ax, vn, an);
+      if (lh == 0) {
+        const size_t o = ((size_t)rec * (p.N >> 1) + c) * 2;
+        p.pool_val[o] = vx; p.pool_val[o + 1] = vn;
+        p.pool_arg[o] = ax; p.pool_arg[o + 1] = an;
+      }
+    }
   } else {  // SPGAN_EPI_BNBWD (/ SPGAN_WIDE_EPI_BNBWD_GOUT)
     constexpr bool GOUT = EPI == SPGAN_WIDE_EPI_BNBWD_GOUT;
     static_assert(EPI == SPGAN_EPI_BNBWD || GOUT, "unknown epilogue");

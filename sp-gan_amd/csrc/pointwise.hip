@@ -19,11 +19,13 @@ __global__ void adain_fwd_kernel(const float* __restrict__ x, size_t M, int C, i
   out[t] = fmaf(gb[m * 2 * C + c], xh, gb[m * 2 * C + C + c]);
 }
 
+// gamma[m, c] = gb[m * ldg + c] (the [M,2C] style tensor: ldg = 2C; a gamma-only tensor: ldg = C); shape b's x rows start at x + b * xs
+// (xs = N*C: a dense [M,C] tensor; 0: every shape has the same rows).
 // stage 1: dgb = [dout*xhat | dout];  partials over each shape's N rows of (sum dxh, sum dxh*xhat), dxh = dout*gamma
 __global__ __launch_bounds__(256) void adain_bwd1_kernel(const float* __restrict__ dout, const float* __restrict__ x, int C, int N, float slope,
                                                          const float* __restrict__ imean, const float* __restrict__ ivar, float eps,
-                                                         const float* __restrict__ gb, int tiles_per_group, float* __restrict__ dgb,
-                                                         float* __restrict__ part) {
+                                                         const float* __restrict__ gb, int ldg, size_t xs, int tiles_per_group,
+                                                         float* __restrict__ dgb, float* __restrict__ part) {
   __shared__ float r0[4][64], r1[4][64];
   const int tile = blockIdx.x;
   const int b = tile / tiles_per_group, q = tile % tiles_per_group;
@@ -37,10 +39,10 @@ __global__ __launch_bounds__(256) void adain_bwd1_kernel(const float* __restrict
     for (int r = sl; r < cnt; r += 4) {  // (two stores per row: unrolling this one by 8 made it slower, 30 -> 46 us)
       const size_t m = (size_t)b * N + n0 + r;
       const float d = dout[m * C + c];
-      const float xh = (lrelu_f(x[m * C + c], slope) - mu) * iv;
+      const float xh = (lrelu_f(x[(size_t)b * xs + (size_t)(n0 + r) * C + c], slope) - mu) * iv;
       dgb[m * 2 * C + c] = d * xh;
       dgb[m * 2 * C + C + c] = d;
-      const float dxh = d * gb[m * 2 * C + c];
+      const float dxh = d * gb[m * ldg + c];
       s0 += dxh;
       s1 = fmaf(dxh, xh, s1);
     }
@@ -57,16 +59,16 @@ __global__ __launch_bounds__(256) void adain_bwd1_kernel(const float* __restrict
 // stage 2: dx = invstd * (dxh - S0/N - xhat*S1/N) * lrelu'(x)
 __global__ void adain_bwd2_kernel(const float* __restrict__ dout, const float* __restrict__ x, size_t M, int C, int N, float slope,
                                   const float* __restrict__ imean, const float* __restrict__ ivar, float eps, const float* __restrict__ gb,
-                                  const float* __restrict__ S0, const float* __restrict__ S1, float* __restrict__ dx) {
+                                  int ldg, size_t xs, const float* __restrict__ S0, const float* __restrict__ S1, float* __restrict__ dx) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= M * C) return;
   const size_t m = t / C;
   const int c = t % C;
   const size_t b = m / N;
-  const float xv = x[t];
+  const float xv = x[b * xs + (m - b * N) * C + c];
   const float iv = rsqrtf(ivar[b * C + c] + eps);
   const float xh = (lrelu_f(xv, slope) - imean[b * C + c]) * iv;
-  const float dxh = dout[t] * gb[m * 2 * C + c];
+  const float dxh = dout[t] * gb[m * ldg + c];
   const float rn = 1.0f / (float)N;
   dx[t] = iv * (dxh - S0[b * C + c] * rn - xh * (S1[b * C + c] * rn)) * lrelu_mask(xv, slope);
 }
@@ -644,20 +646,21 @@ extern "C" int spgan_adain_fwd(const float* x, int M, int C, int N, float slope,
 }
 
 extern "C" int spgan_adain_bwd1(const float* dout, const float* x, int M, int C, int N, float slope, const float* imean, const float* ivar,
-                                float eps, const float* gb, float* dgb, float* partials, spgan_stream_t s_) {
-  SPGAN_CHECK_ARG(dout && x && imean && ivar && gb && dgb && partials && M > 0 && C > 0 && N > 0 && M % N == 0);
+                                float eps, const float* gb, int ld_gamma, long x_shape_stride, float* dgb, float* partials, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(dout && x && imean && ivar && gb && dgb && partials && M > 0 && C > 0 && N > 0 && M % N == 0 && ld_gamma >= C && x_shape_stride >= 0);
   const int tpg = cdiv(N, RT);
   hipLaunchKernelGGL(adain_bwd1_kernel, dim3((M / N) * tpg, cdiv(C, 64)), dim3(256), 0, (hipStream_t)s_, dout, x, C, N, slope, imean, ivar, eps,
-                     gb, tpg, dgb, partials);
+                     gb, ld_gamma, (size_t)x_shape_stride, tpg, dgb, partials);
   return spgan_launch_status();
 }
 
 extern "C" int spgan_adain_bwd2(const float* dout, const float* x, int M, int C, int N, float slope, const float* imean, const float* ivar,
-                                float eps, const float* gb, const float* S0, const float* S1, float* dx, spgan_stream_t s_) {
-  SPGAN_CHECK_ARG(dout && x && imean && ivar && gb && S0 && S1 && dx && M > 0 && C > 0 && N > 0 && M % N == 0);
+                                float eps, const float* gb, int ld_gamma, long x_shape_stride, const float* S0, const float* S1, float* dx,
+                                spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(dout && x && imean && ivar && gb && S0 && S1 && dx && M > 0 && C > 0 && N > 0 && M % N == 0 && ld_gamma >= C && x_shape_stride >= 0);
   const size_t total = (size_t)M * C;
   hipLaunchKernelGGL(adain_bwd2_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)s_, dout, x, (size_t)M, C, N, slope, imean, ivar, eps,
-                     gb, S0, S1, dx);
+                     gb, ld_gamma, (size_t)x_shape_stride, S0, S1, dx);
   return spgan_launch_status();
 }
 

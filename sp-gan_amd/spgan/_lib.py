@@ -52,6 +52,9 @@ class GemmNTArgs(C.Structure):
         ("a_half", C.c_int), ("y_bf16", C.c_int), ("y_half", C.c_int),
         ("w_image", C.c_void_p),
         ("gout_add", c_f32p), ("ld_gout_add", C.c_int), ("gout_scale", c_f32p),
+        ("ad_x", c_f32p), ("ad_ldx", C.c_int), ("ad_x_shape_stride", C.c_long), ("ad_rows", C.c_int),
+        ("ad_mean", c_f32p), ("ad_var", c_f32p), ("ad_eps", C.c_float), ("ad_slope", C.c_float),
+        ("ad_gamma", c_f32p), ("ad_ld_gamma", C.c_int), ("ad_gamma_row0", C.c_int),
     ]
 
 
@@ -219,8 +222,8 @@ SIGNATURES = {
     "spgan_edge_scatter_b": (I, [P, P, P, I, I, I, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "spgan_edge_scatter": (I, [P, P, P, I, I, I, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "spgan_adain_fwd": (I, [P, I, I, I, F, P, P, F, P, P, P]),
-    "spgan_adain_bwd1": (I, [P, P, I, I, I, F, P, P, F, P, P, P, P]),
-    "spgan_adain_bwd2": (I, [P, P, I, I, I, F, P, P, F, P, P, P, P, P]),
+    "spgan_adain_bwd1": (I, [P, P, I, I, I, F, P, P, F, P, I, C.c_long, P, P, P]),
+    "spgan_adain_bwd2": (I, [P, P, I, I, I, F, P, P, F, P, I, C.c_long, P, P, P, P]),
     "spgan_pool_bwd_stats": (I, [P, P, P, P, I, P, P, F, I, I, P, P, P]),
     "spgan_pool_bwd_stats_prep": (I, [P, P, P, P, I, P, P, F, I, I, P, I, P, P, P, P, P, P]),
     "spgan_bn_bwd_apply_sparse": (I, [P, P, P, I, I, I, I, P, P, P, P, I, P, P]),

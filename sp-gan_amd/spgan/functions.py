@@ -567,6 +567,7 @@ class RepeatRowsFn(Function):
     @staticmethod
     def backward(ctx, g):
         B = ctx.B
+        g = g.reshape(-1, g.shape[-1])          # (a [B,N,C] gradient where the forward handed out the expanded view of the one block)
         M, Cn = g.shape
         return ops.colsum(g.contiguous().view(B, (M // B) * Cn))[0].view(M // B, Cn), None, None
 
@@ -585,6 +586,7 @@ class AdaINFn(Function):
         else:
             out, actx = nets.adain_forward(P, holder.prefix, x.contiguous(), style.contiguous(), holder.N, holder.slope)
         ctx.holder, ctx.actx = holder, actx
+        ctx.x_shape = x.shape
         ctx.save_for_backward(w, b)
         return out
 
@@ -605,6 +607,8 @@ class AdaINFn(Function):
         if chain is not None and ctx.needs_input_grad[2] and chain[1] == "first":
             chain[0]["ds"] = ds
             ds = None
+        if dx is not None and dx.shape != ctx.x_shape:     # x was the [B,N,C] expanded view of one shared block (nets.g_pair_forward)
+            dx = dx.view(ctx.x_shape)
         return (None, dx, ds) + _deliver((w, b), [g.get(pre + ".style.weight"), g.get(pre + ".style.bias")], ctx.needs_input_grad[3:], ctx.fused)
 
 

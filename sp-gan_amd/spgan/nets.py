@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import ops
+from . import adain_epi, ops
 
 Tensor = torch.Tensor
 NEG = 0.01     # Generator.py:22, Discriminator.py:19
@@ -1149,8 +1149,25 @@ def edgeblock_backward(P, pre: str, ctx, dout: Tensor, csr: Tuple[Tensor, Tensor
 # =============================================================================================
 # AdaptivePointNorm (Generator.py:24-45) with the preceding LeakyReLU(0.2) optionally fused (slope)
 # =============================================================================================
-def adain_forward(P, pre: str, x: Tensor, style: Tensor, N: int, slope: float = 1.0):
+def adain_forward(P, pre: str, x: Tensor, style: Tensor, N: int, slope: float = 1.0, fused: Optional[dict] = None):
+    """fused = dict(gamma_row0=r, pool=bool) asks for the normalisation inside the style GEMM's epilogue (adain_epi.py) where that launch
+    takes the layer: [gamma|beta] is never stored, gamma alone is kept for the rows r.. (those whose backward will run), x may be the one
+    [N,C] block all shapes share, and with pool the context carries the per-tile max records of the output ("pool").  Otherwise, and
+    always on CPU tensors, the chain GEMM -> statistics -> adain_fwd on a dense x."""
     Ws, bs = _w2(P[pre + ".style.weight"]), P[pre + ".style.bias"]
+    M = style.shape[0]
+    if fused is not None and adain_epi.usable(x, style, Ws, N):
+        if x.shape[0] != M:                                                      # one [N,C] block for every shape: statistics of the one copy
+            imean, ivar = adain_epi.shared_stats(x, slope, M // N)
+        else:
+            imean, ivar = ops.colstats(x, N, slope)
+            imean = imean.contiguous(); ivar = ivar.contiguous()
+        pool = bool(fused.get("pool")) and adain_epi.can_pool(M, N)
+        r0 = fused.get("gamma_row0", 0)
+        out, gamma, rec = adain_epi.forward(x, style, Ws, bs, N, slope, imean, ivar, gamma_row0=r0, pool=pool)
+        return out, dict(x=x, style=style, gb=None, gamma=gamma, gamma_row0=r0, imean=imean, ivar=ivar, N=N, slope=slope, pool=rec)
+    if x.shape[0] != M:
+        x = x.repeat(M // N, 1)
     gb = ops.gemm_nt(style, Ws, bs)                                              # [M, 2C] = [gamma | beta]
     imean, ivar = ops.colstats(x, N, slope)
     imean = imean.contiguous(); ivar = ivar.contiguous()
@@ -1160,7 +1177,10 @@ def adain_forward(P, pre: str, x: Tensor, style: Tensor, N: int, slope: float = 
 
 def adain_backward(P, pre: str, ctx, dout: Tensor, need_dx: bool = True, need_dstyle: bool = True, need_dparams: bool = True,
                    dstyle_addend: Optional[Tensor] = None):
-    dx, dgb = ops.adain_bwd(dout.contiguous(), ctx["x"], ctx["N"], ctx["slope"], ctx["imean"], ctx["ivar"], ctx["gb"])
+    if ctx.get("gamma") is not None:                                            # the fused forward kept gamma alone (adain_epi.py)
+        dx, dgb = adain_epi.backward(dout.contiguous(), ctx["x"], ctx["N"], ctx["slope"], ctx["imean"], ctx["ivar"], ctx["gamma"])
+    else:
+        dx, dgb = ops.adain_bwd(dout.contiguous(), ctx["x"], ctx["N"], ctx["slope"], ctx["imean"], ctx["ivar"], ctx["gb"])
     g = {}
     if need_dparams:
         gws, g[pre + ".style.bias"] = ops.gemm_tn(dgb, ctx["style"], defer=True, with_colsum=True)
@@ -1265,8 +1285,10 @@ def g_pair_forward(Ph, Pa1, Pe2, bufs_e2, Pa2, Pgt, bufs_g, x_pm2: Tensor, zb2: 
     c = x_pm2.shape[1]
     rb = ops.gemm_nt(zb2.contiguous(), _cols_from(W0, c), Ph["head.0.bias"])                           # [2B,128]: the latent half of head.0
     style, mh = mlp_forward(Ph, ["head.0", "head.2"], [ops.ACT_LRELU, ops.ACT_LRELU], x_pm2, NEG, rowbias=rb, N=N, first_weight=W0[:, :c])
-    x1 = x1_one.repeat(2 * B, 1)                                                                       # the same EdgeConv1 rows for every shape of both passes
-    a1, c1 = adain_forward(Pa1, "a", x1, style, N, slope)
+    # the same EdgeConv1 rows for every shape of both passes: the fused AdaIN launch reads the one block (gamma kept for pass 1's rows only:
+    # pass 0 has no backward); the chain materialises the 2B copies
+    a1, c1 = adain_forward(Pa1, "a", x1_one.contiguous(), style, N, slope, fused=dict(gamma_row0=M))
+    x1 = c1["x"]
     F_ = _w2(Pe2["e.conv_x.0.weight"]).shape[0]
     x2 = torch.empty((2 * M, F_), dtype=torch.float32, device=x_pm2.device)
     ec = []
@@ -1275,9 +1297,13 @@ def g_pair_forward(Ph, Pa1, Pe2, bufs_e2, Pa2, Pgt, bufs_g, x_pm2: Tensor, zb2: 
         xin = a1[rows]
         idx = idx2[p_] if (idx2 is not None and idx2[p_] is not None) else ops.knn(xin, B, N, k, 0)
         ec.append(edgeblock_forward(Pe2, bufs_e2, "e", xin, idx, B, N, training, True, out=x2[rows]))
-    a2, c2 = adain_forward(Pa2, "a", x2, style, N, slope)
+    a2, c2 = adain_forward(Pa2, "a", x2, style, N, slope, fused=dict(gamma_row0=M, pool=True))
     Wt0 = Pgt["tail.0.weight"].view(Pgt["tail.0.weight"].shape[0], -1)
-    gcs = [global_forward(Pgt, bufs_g, a2[p_ * M:(p_ + 1) * M], B, N, training, True) for p_ in (0, 1)]
+    pooled = [None, None]
+    if c2.get("pool") is not None:                                                                     # the max over N of both passes from the epilogue's records
+        gmax2, garg2 = adain_epi.pool_from_records(c2["pool"], 2 * B, N, groups=2)
+        pooled = [(gmax2[p_ * B:(p_ + 1) * B], garg2[p_ * B:(p_ + 1) * B]) for p_ in (0, 1)]
+    gcs = [global_forward(Pgt, bufs_g, a2[p_ * M:(p_ + 1) * M], B, N, training, True, pooled=pooled[p_]) for p_ in (0, 1)]
     Cg = gcs[0]["y3"].shape[1]
     rb2 = torch.empty((2 * B, Wt0.shape[0]), dtype=torch.float32, device=x_pm2.device)
     for p_ in (0, 1):
@@ -1289,8 +1315,11 @@ def g_pair_forward(Ph, Pa1, Pe2, bufs_e2, Pa2, Pgt, bufs_g, x_pm2: Tensor, zb2: 
         return dict(m, x=m["x"][M:], hs=[h[M:] for h in m["hs"]])
 
     def half_adain(cx):
-        return dict(cx, x=cx["x"][M:], style=cx["style"][M:], gb=cx["gb"][M:], imean=cx["imean"][B:], ivar=cx["ivar"][B:])
-    return dict(fake_d=out[:M], head=(style[M:], half_mlp(mh)), x1=x1[M:], adain1=(a1[M:], half_adain(c1)), ec2=ec[1],
+        xs = cx["x"] if cx["x"].shape[0] != 2 * M else cx["x"][M:]                                     # (the shared [N,C] block serves either pass)
+        return dict(cx, x=xs, style=cx["style"][M:], gb=None if cx["gb"] is None else cx["gb"][M:], imean=cx["imean"][B:], ivar=cx["ivar"][B:],
+                    pool=None)
+    x1_half = x1[M:] if x1.shape[0] == 2 * M else x1.unsqueeze(0).expand(B, N, x1.shape[1])            # pass 1's copies: a view in either case
+    return dict(fake_d=out[:M], head=(style[M:], half_mlp(mh)), x1=x1_half, adain1=(a1[M:], half_adain(c1)), ec2=ec[1],
                 adain2=(a2[M:], half_adain(c2)), tail=(out[M:], gcs[1], half_mlp(mt)), idx=(ec[0][1]["idx"], ec[1][1]["idx"]),
                 x1_in=a1[M:], a2=a2[M:])
 
@@ -1342,10 +1371,11 @@ def attention_backward(P, pre: str, ctx, dy: Tensor, need_dx: bool = True):
     return dx, g
 
 
-def global_forward(P, bufs, a2: Tensor, B: int, N: int, training: bool = True, update_running: bool = True):
+def global_forward(P, bufs, a2: Tensor, B: int, N: int, training: bool = True, update_running: bool = True, pooled=None):
     """max over N -> Linear+BN1d+LReLU -> Linear+BN1d+LReLU (Generator.py:119-126,183-186).  Returns the
-    second pre-BN tensor and its BN affine (the activation is applied by the consumer's prologue)."""
-    gmax, garg = ops.maxpool(a2, B, N)
+    second pre-BN tensor and its BN affine (the activation is applied by the consumer's prologue).
+    pooled = (gmax, garg): the max over N and its rows when a2's producer already delivered them (adain_epi.pool_from_records)."""
+    gmax, garg = pooled if pooled is not None else ops.maxpool(a2, B, N)
     W0, b0 = P["global_conv.0.weight"], P["global_conv.0.bias"]
     W3, b3 = P["global_conv.3.weight"], P["global_conv.3.bias"]
     y0, bn0 = _gemm_bn(gmax, W0, b0, P, bufs, "global_conv.1", B, training, update_running)

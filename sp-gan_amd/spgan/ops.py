@@ -1859,10 +1859,10 @@ def adain_bwd(dout: Tensor, x: Tensor, N: int, slope: float, imean: Tensor, ivar
     dgb = torch.empty_like(gb)
     part = torch.empty((B * tpg, Cn, 2), dtype=torch.float32, device=x.device)
     lib = _lib.load()
-    check(lib.spgan_adain_bwd1(_p(dout), _p(x), M_, Cn, N, float(slope), _p(imean), _p(ivar), BN_EPS, _p(gb), _p(dgb), _p(part), _s()), "adain_bwd1")
+    check(lib.spgan_adain_bwd1(_p(dout), _p(x), M_, Cn, N, float(slope), _p(imean), _p(ivar), BN_EPS, _p(gb), 2 * Cn, N * Cn, _p(dgb), _p(part), _s()), "adain_bwd1")
     S0, S1 = _finalize(part, B, tpg, Cn, N, 1)
     dx = torch.empty_like(x)
-    check(lib.spgan_adain_bwd2(_p(dout), _p(x), M_, Cn, N, float(slope), _p(imean), _p(ivar), BN_EPS, _p(gb), _p(S0), _p(S1), _p(dx), _s()), "adain_bwd2")
+    check(lib.spgan_adain_bwd2(_p(dout), _p(x), M_, Cn, N, float(slope), _p(imean), _p(ivar), BN_EPS, _p(gb), 2 * Cn, N * Cn, _p(S0), _p(S1), _p(dx), _s()), "adain_bwd2")
     return dx, dgb
 
 
