@@ -718,6 +718,22 @@ int spgan_edge_max_bwd_point(float* g, const uint8_t* sel, const float* PQ, int 
 int spgan_edge_max_bwd_graph(const float* r, const uint8_t* sel, const float* PQ, int ld, const int32_t* rowptr, const int32_t* src,
                              const int32_t* idx, int M, int k, int F, const float* scale, const float* mean, const float* invstd,
                              const float* sums, float* dPQ, int ldd, spgan_stream_t s);
+/* The second derivative of the max-aggregation edge convolution through dx: v is the cotangent of dx, point-major,
+ * VPQ [M, ldv >= 2F] = [VP | VQ] = v Wst^T (no bias); the edge value of v is t(i,j) = VQ[i] + VP[idx[i,j]], gathered exactly like the pre-norm
+ * value z.  r, sel, PQ, idx: as in the first backward (r = g * 1[out > 0]).  Same determinism: fixed summation orders, no float atomics.
+ *   spgan_edge_max_dbl_point: two sets of plain-sum records [ceil(M / tile_points)][F][2] (finalize mode 1, tile_rows = tile_points):
+ *                             partials_t = (T1, T2) = (sum_e t_e, sum_e t_e * xhat_e) over the point's own k edges -- train mode; NULL with
+ *                             mean, invstd NULL in eval mode, where the statistics are constants and no edge sum is needed --, and
+ *                             partials_s = (S, 0) = sum_i r_i * t(i, sel).
+ *   spgan_edge_max_dbl_graph: ghat [M,F], the cotangent of the incoming cotangent g, and, in train mode, PQbar [M, ldb >= 2F] = [Pbar | Qbar],
+ *                             the cotangent of PQ, over the in-edge lists of spgan_csr_build.  sums = [s1 | s2] of the first backward,
+ *                             dsums = [T1 | T2 | S] (3F): train mode (mean, invstd, rowptr, src, PQbar required).  Both NULL: eval mode,
+ *                             ghat = 1[out > 0] * scale * t(i, sel) and nothing else (rowptr, src, PQbar NULL). */
+int spgan_edge_max_dbl_point(const float* r, const uint8_t* sel, const float* PQ, int ld, const float* VPQ, int ldv, const int32_t* idx, int M,
+                             int k, int F, const float* mean, const float* invstd, float* partials_t, float* partials_s, spgan_stream_t s);
+int spgan_edge_max_dbl_graph(const float* r, const uint8_t* sel, const float* PQ, int ld, const float* VPQ, int ldv, const int32_t* rowptr,
+                             const int32_t* src, const int32_t* idx, int M, int k, int F, const float* scale, const float* mean,
+                             const float* invstd, const float* sums, const float* dsums, float* ghat, float* PQbar, int ldb, spgan_stream_t s);
 /* Rank-window edge convolution (csrc/edge_window.hip): the [1,w] Conv2d layers of upsample_edgeConv (Generation/modules.py:799-845) over
  * get_edge_features(x), as fp32 MFMA products over gathered neighbour rows.  x [M, ldx >= C] point-major, idx int32 [M,k] global rows
  * (a row outside [0,M) counts as the point itself: a zero difference), 1 <= w <= k <= 28, T = k - w + 1 window positions per point,

@@ -13,6 +13,8 @@
 //   finish   picks max or min by the sign of a_c, writes out[M,F] and the selected rank (bit 7 set: clipped by the ReLU).
 //   bwd_point  r = g * 1[out > 0] in place, and the plain-sum records of (sum r, sum r*xhat_sel)  ->  d beta, d gamma.
 //   bwd_graph  dQ per point and dP over the reverse CSR (in-edge lists in ascending edge order: no float atomics, reproducible sums).
+//   dbl_point / dbl_graph  the second derivative through dx (opt-in: edgeConv(double_backward=True)): the same two passes with the
+//            direction's per-point product VPQ = v Wst^T as a second operand.
 //
 // Thread mapping: a workgroup owns EM_PT consecutive points; a thread owns V consecutive channels (V = 4: 16-byte loads of P, Q, r) of
 // the points p = slot, slot + nslots, ...  Workgroups are dealt so that an XCD works through a contiguous eighth of the points.
@@ -354,6 +356,209 @@ __global__ __launch_bounds__(256) void edge_max_bwd_graph_kernel(const float* __
   }
 }
 
+// ------------------------------------------------------------------------------------------ double backward: the edge sums of the direction
+// VPQ [M, >= 2F] = [VP | VQ] = v Wst^T; t(i,j) = VQ_i + VP_n(i,j) is gathered like the pre-norm value.  part_t [tiles][F][2] = (sum_e t_e,
+// sum_e t_e * xhat_e) over the tile's own edges (NULL: eval mode, no edge sum is needed), part_s [tiles][F][2] = (sum_i r_i * t(i, sel), 0).
+template <int V>
+__global__ __launch_bounds__(256) void edge_max_dbl_point_kernel(const float* __restrict__ r, const uint8_t* __restrict__ sel, const float* __restrict__ PQ,
+                                                                 int ld, const float* __restrict__ VPQ, int ldvq, const int32_t* __restrict__ idx, int M,
+                                                                 int k, int F, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                 float* __restrict__ part_t, float* __restrict__ part_s) {
+  __shared__ float red[3][256 * V];
+  const int bx = xcd_block();
+  const int p0 = bx * EM_PT;
+  if (p0 >= M) return;
+  const int np = min(EM_PT, M - p0);
+  const Lanes L = lanes_of(F, V);
+  for (int c0 = 0; c0 < F; c0 += L.QFp * V) {
+    const int c = c0 + L.q * V;
+    const bool ok = c < F;
+    float s1[V], s2[V], s3[V];
+#pragma unroll
+    for (int u = 0; u < V; ++u) s1[u] = s2[u] = s3[u] = 0.f;
+    if (ok) {
+      float mu[V], iv[V];
+#pragma unroll
+      for (int u = 0; u < V; ++u) mu[u] = iv[u] = 0.f;
+      if (part_t) {   // a kernel argument: uniform
+        ldv<V>(mean + c, mu); ldv<V>(invstd + c, iv);
+      }
+      for (int p = L.slot; p < np; p += L.nslots) {
+        const int i = p0 + p;
+        const int32_t* nb = idx + (size_t)i * k;
+        const size_t o = (size_t)i * F + c;
+        float rv[V], vq[V];
+        int sv[V];
+        ldv<V>(r + o, rv); ldb<V>(sel + o, sv);
+        ldv<V>(VPQ + (size_t)i * ldvq + F + c, vq);
+        if (part_t) {
+          float qv[V];
+          ldv<V>(PQ + (size_t)i * ld + F + c, qv);
+#pragma unroll 4
+          for (int rr = 0; rr < k; ++rr) {
+            float pv[V], vp[V];
+            ldv<V>(PQ + (size_t)nb[rr] * ld + c, pv);
+            ldv<V>(VPQ + (size_t)nb[rr] * ldvq + c, vp);
+#pragma unroll
+            for (int u = 0; u < V; ++u) {
+              const float t = vq[u] + vp[u];
+              s1[u] += t;
+              s2[u] = fmaf(t, ((qv[u] + pv[u]) - mu[u]) * iv[u], s2[u]);
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+          if (!(sv[u] & EM_CLIPPED)) {                                  // r is zero where the ReLU clipped
+            const int n = nb[sv[u]];                                    // the selected neighbour differs from channel to channel
+            s3[u] = fmaf(rv[u], vq[u] + VPQ[(size_t)n * ldvq + c + u], s3[u]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+      red[0][threadIdx.x * V + u] = s1[u];
+      red[1][threadIdx.x * V + u] = s2[u];
+      red[2][threadIdx.x * V + u] = s3[u];
+    }
+    __syncthreads();
+    if (L.slot == 0 && ok) {
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        float t1 = 0.f, t2 = 0.f, t3 = 0.f;
+        for (int s = 0; s < L.nslots; ++s) {      // fixed order
+          t1 += red[0][(s * L.QFp + L.q) * V + u];
+          t2 += red[1][(s * L.QFp + L.q) * V + u];
+          t3 += red[2][(s * L.QFp + L.q) * V + u];
+        }
+        const size_t o = ((size_t)bx * F + c + u) * 2;
+        if (part_t) {
+          part_t[o] = t1;
+          part_t[o + 1] = t2;
+        }
+        part_s[o] = t3;
+        part_s[o + 1] = 0.f;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------------ double backward: ghat per point, PQbar over the in-edges
+// With E = M*k, cc = a*invstd/E, A = S - s1*T1/E - s2*T2/E the cotangent of the (never stored) edge value z_e is
+//   zbar_e = K0 + K1*xhat_e + K2*t_e + K3*r_i*d(e = e*(i)),
+//   K0 = cc*(T2*s1 + s2*T1)/E,  K1 = cc*(2*s2*T2/E - A),  K2 = -cc*s2,  K3 = -cc*T2,
+// so, as in edge_max_bwd_graph_kernel with VPQ as a second operand,
+//   Qbar(i,c) = k*K0 + K1*invstd*(k*(Q - mean) + sum_j P_n) + K2*(k*VQ + sum_j VP_n) + K3*r
+//   Pbar(m,c) = deg*K0 + K1*invstd*(sum_{(i,j)->m} Q_i + deg*(P_m - mean)) + K2*(sum_{(i,j)->m} VQ_i + deg*VP_m) + K3*sum_{(i,j)->m, j = sel(i,c)} r(i,c)
+//   ghat(i,c) = 1[out > 0] * a * (t_sel - T1/E - xhat_sel*T2/E).
+// sums == NULL (eval mode: the statistics are constants): ghat = 1[out > 0] * a * t_sel and there is no PQbar.
+template <int V>
+__global__ __launch_bounds__(256) void edge_max_dbl_graph_kernel(const float* __restrict__ r, const uint8_t* __restrict__ sel, const float* __restrict__ PQ,
+                                                                 int ld, const float* __restrict__ VPQ, int ldvq, const int32_t* __restrict__ rowptr,
+                                                                 const int32_t* __restrict__ src, const int32_t* __restrict__ idx, int M, int k, int F,
+                                                                 const float* __restrict__ scale, const float* __restrict__ mean,
+                                                                 const float* __restrict__ invstd, const float* __restrict__ sums,
+                                                                 const float* __restrict__ dsums, float rE, float* __restrict__ ghat,
+                                                                 float* __restrict__ PQbar, int ldbar) {
+  const int bx = xcd_block();
+  const int p0 = bx * EM_PT;
+  if (p0 >= M) return;
+  const int np = min(EM_PT, M - p0);
+  const Lanes L = lanes_of(F, V);
+  const float kf = (float)k;
+  for (int c0 = 0; c0 < F; c0 += L.QFp * V) {
+    const int c = c0 + L.q * V;
+    if (c >= F) continue;
+    float a[V], mu[V], K0[V], K1[V], K2[V], K3[V], g1[V], g2[V];
+    ldv<V>(scale + c, a);
+#pragma unroll
+    for (int u = 0; u < V; ++u) mu[u] = K0[u] = K1[u] = K2[u] = K3[u] = g1[u] = g2[u] = 0.f;
+    if (sums) {
+      float iv[V], s1[V], s2[V], T1[V], T2[V], S[V];
+      ldv<V>(mean + c, mu); ldv<V>(invstd + c, iv);
+      ldv<V>(sums + c, s1); ldv<V>(sums + F + c, s2);
+      ldv<V>(dsums + c, T1); ldv<V>(dsums + F + c, T2); ldv<V>(dsums + 2 * F + c, S);
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        const float A = S[u] - s1[u] * T1[u] * rE - s2[u] * T2[u] * rE;
+        const float cc = a[u] * iv[u] * rE;
+        K0[u] = cc * (T2[u] * s1[u] + s2[u] * T1[u]) * rE;
+        K1[u] = cc * (2.f * s2[u] * T2[u] * rE - A) * iv[u];          // times invstd: xhat = (z - mean) * invstd
+        K2[u] = -cc * s2[u];
+        K3[u] = -cc * T2[u];
+        g1[u] = T1[u] * rE;
+        g2[u] = T2[u] * rE * iv[u];
+      }
+    }
+    for (int p = L.slot; p < np; p += L.nslots) {
+      const int m = p0 + p;
+      const int32_t* nb = idx + (size_t)m * k;
+      float rm[V], qm[V], vqm[V], gh[V];
+      int sm[V];
+      ldv<V>(r + (size_t)m * F + c, rm); ldb<V>(sel + (size_t)m * F + c, sm);
+      ldv<V>(PQ + (size_t)m * ld + F + c, qm);
+      ldv<V>(VPQ + (size_t)m * ldvq + F + c, vqm);
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        gh[u] = 0.f;
+        if (!(sm[u] & EM_CLIPPED)) {
+          const int n = nb[sm[u]];
+          const float ts = vqm[u] + VPQ[(size_t)n * ldvq + c + u];
+          const float zs = (qm[u] + PQ[(size_t)n * ld + c + u]) - mu[u];
+          gh[u] = a[u] * ((ts - g1[u]) - zs * g2[u]);
+        }
+      }
+      stv<V>(ghat + (size_t)m * F + c, gh);
+      if (!sums) continue;
+      const int t0 = rowptr[m], t1 = rowptr[m + 1];
+      float acc[V], sq[V], svq[V];
+#pragma unroll
+      for (int u = 0; u < V; ++u) acc[u] = sq[u] = svq[u] = 0.f;
+      for (int t = t0; t < t1; ++t) {          // ascending edge ids: a fixed summation order
+        const int e = src[t];
+        const int i = e / k, j = e - i * k;
+        float rv[V], qv[V], vq[V];
+        int sv[V];
+        ldv<V>(r + (size_t)i * F + c, rv); ldb<V>(sel + (size_t)i * F + c, sv);
+        ldv<V>(PQ + (size_t)i * ld + F + c, qv);
+        ldv<V>(VPQ + (size_t)i * ldvq + F + c, vq);
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+          acc[u] += (sv[u] & (EM_CLIPPED - 1)) == j ? rv[u] : 0.f;   // r is zero where the ReLU clipped
+          sq[u] += qv[u];
+          svq[u] += vq[u];
+        }
+      }
+      const float deg = (float)(t1 - t0);
+      float pm[V], vpm[V], ps[V], vps[V], bP[V], bQ[V];
+      ldv<V>(PQ + (size_t)m * ld + c, pm);
+      ldv<V>(VPQ + (size_t)m * ldvq + c, vpm);
+#pragma unroll
+      for (int u = 0; u < V; ++u) ps[u] = vps[u] = 0.f;
+#pragma unroll 4
+      for (int rr = 0; rr < k; ++rr) {
+        float pv[V], vp[V];
+        ldv<V>(PQ + (size_t)nb[rr] * ld + c, pv);
+        ldv<V>(VPQ + (size_t)nb[rr] * ldvq + c, vp);
+#pragma unroll
+        for (int u = 0; u < V; ++u) {
+          ps[u] += pv[u];
+          vps[u] += vp[u];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        bQ[u] = kf * K0[u] + K1[u] * (kf * (qm[u] - mu[u]) + ps[u]) + K2[u] * (kf * vqm[u] + vps[u]) + K3[u] * rm[u];
+        bP[u] = deg * K0[u] + K1[u] * (sq[u] + deg * (pm[u] - mu[u])) + K2[u] * (svq[u] + deg * vpm[u]) + K3[u] * acc[u];
+      }
+      stv<V>(PQbar + (size_t)m * ldbar + c, bP);
+      stv<V>(PQbar + (size_t)m * ldbar + F + c, bQ);
+    }
+  }
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 inline bool sizes_ok(int M, int k, int F, int ld) {
@@ -417,5 +622,41 @@ extern "C" int spgan_edge_max_bwd_graph(const float* r, const uint8_t* sel, cons
     hipLaunchKernelGGL(edge_max_bwd_graph_kernel<4>, gr, b, 0, (hipStream_t)s_, r, sel, PQ, ld, rowptr, src, idx, M, k, F, scale, mean, invstd, sums, rE, dPQ, ldd);
   else
     hipLaunchKernelGGL(edge_max_bwd_graph_kernel<1>, gr, b, 0, (hipStream_t)s_, r, sel, PQ, ld, rowptr, src, idx, M, k, F, scale, mean, invstd, sums, rE, dPQ, ldd);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_edge_max_dbl_point(const float* r, const uint8_t* sel, const float* PQ, int ld, const float* VPQ, int ldvq, const int32_t* idx,
+                                        int M, int k, int F, const float* mean, const float* invstd, float* partials_t, float* partials_s,
+                                        spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(r && sel && PQ && VPQ && idx && partials_s && sizes_ok(M, k, F, ld) && ldvq >= 2 * F);
+  if (partials_t) SPGAN_CHECK_ARG(mean && invstd);         // train mode
+  else SPGAN_CHECK_ARG(!mean && !invstd);
+  const dim3 gr(grid8(cdiv(M, EM_PT))), b(256);
+  const bool v4 = F % 4 == 0 && ld % 4 == 0 && ldvq % 4 == 0 && al16(PQ) && al16(VPQ) && al16(r) && al4(sel) &&
+                  (!partials_t || (al16(mean) && al16(invstd)));
+  if (v4)
+    hipLaunchKernelGGL(edge_max_dbl_point_kernel<4>, gr, b, 0, (hipStream_t)s_, r, sel, PQ, ld, VPQ, ldvq, idx, M, k, F, mean, invstd, partials_t, partials_s);
+  else
+    hipLaunchKernelGGL(edge_max_dbl_point_kernel<1>, gr, b, 0, (hipStream_t)s_, r, sel, PQ, ld, VPQ, ldvq, idx, M, k, F, mean, invstd, partials_t, partials_s);
+  return spgan_launch_status();
+}
+
+extern "C" int spgan_edge_max_dbl_graph(const float* r, const uint8_t* sel, const float* PQ, int ld, const float* VPQ, int ldvq, const int32_t* rowptr,
+                                        const int32_t* src, const int32_t* idx, int M, int k, int F, const float* scale, const float* mean,
+                                        const float* invstd, const float* sums, const float* dsums, float* ghat, float* PQbar, int ldbar,
+                                        spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(r && sel && PQ && VPQ && idx && scale && ghat && sizes_ok(M, k, F, ld) && ldvq >= 2 * F);
+  if (sums) SPGAN_CHECK_ARG(dsums && mean && invstd && rowptr && src && PQbar && ldbar >= 2 * F);       // train mode
+  else SPGAN_CHECK_ARG(!dsums && !PQbar);
+  const dim3 gr(grid8(cdiv(M, EM_PT))), b(256);
+  const bool v4 = F % 4 == 0 && ld % 4 == 0 && ldvq % 4 == 0 && al16(PQ) && al16(VPQ) && al16(r) && al4(sel) && al16(scale) && al16(ghat) &&
+                  (!sums || (ldbar % 4 == 0 && al16(PQbar) && al16(mean) && al16(invstd) && al16(sums) && al16(dsums)));
+  const float rE = 1.0f / ((float)M * (float)k);
+  if (v4)
+    hipLaunchKernelGGL(edge_max_dbl_graph_kernel<4>, gr, b, 0, (hipStream_t)s_, r, sel, PQ, ld, VPQ, ldvq, rowptr, src, idx, M, k, F, scale, mean, invstd,
+                       sums, dsums, rE, ghat, PQbar, ldbar);
+  else
+    hipLaunchKernelGGL(edge_max_dbl_graph_kernel<1>, gr, b, 0, (hipStream_t)s_, r, sel, PQ, ld, VPQ, ldvq, rowptr, src, idx, M, k, F, scale, mean, invstd,
+                       sums, dsums, rE, ghat, PQbar, ldbar);
   return spgan_launch_status();
 }

@@ -286,6 +286,8 @@ SIGNATURES = {
     "spgan_edge_max_finish": (I, [P, I, P, P, P, P, P, P, I, I, P, P, P]),
     "spgan_edge_max_bwd_point": (I, [P, P, P, I, P, I, I, I, P, P, P, P]),
     "spgan_edge_max_bwd_graph": (I, [P, P, P, I, P, P, P, I, I, I, P, P, P, P, P, I, P]),
+    "spgan_edge_max_dbl_point": (I, [P, P, P, I, P, I, P, I, I, I, P, P, P, P, P]),
+    "spgan_edge_max_dbl_graph": (I, [P, P, P, I, P, I, P, P, P, I, I, I, P, P, P, P, P, P, P, I, P]),
     "spgan_edge_window_tile_points": (I, [I, I]),
     "spgan_edge_window_gemm": (I, [P, I, P, I, I, I, P, I, I, I, P, I, P, I, P, I, P, P]),
     "spgan_edge_window_wgrad_ws_bytes": (SZ, [I, I, I, I, I]),

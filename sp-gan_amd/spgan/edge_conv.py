@@ -12,7 +12,8 @@ The family's conventions, stated once:
   write them between forward and backward, so they ride on ctx instead of through save_for_backward's version check.  The running
   statistics that ARE updated in place are not read by the backward.
 * Once differentiable: a selection or a mask is piecewise constant and the backward is a closed form over saved statistics, so a second
-  derivative is refused where it is asked for (`refuse_double_backward`): no GradientPenalty on top of these layers.
+  derivative is refused where it is asked for (`refuse_double_backward`): no GradientPenalty on top of these layers.  The one exception is
+  opt-in: `edgeConv(double_backward=True)` runs its first backward as a differentiable node (`EdgeMaxConvBwdFn`).
 * The rank layers (RankEdgeConvFn's [1,k] product, all of WeightedRankEdgeConvFn, CoordRankEdgeConvFn and BilateralUpsampleEdgeConvFn) compute exact fp32 products: they do not follow
   ops.set_mfma_operands.
 * Weight-derived operand images are cached per weight set (`cached_images`)."""
@@ -270,7 +271,9 @@ def rank_scatter(da: Tensor, rowptr: Tensor, src: Tensor, st, PQ: Tensor, idx: T
 class EdgeMaxConvFn(Function):
     """out [B,F,N] = max_j relu(bn(conv1x1(cat[x_i, x_j - x_i])))   (the reference's edgeConv, Generation/modules.py:779-796) without the
     [B,2Fin,N,k] edge tensor: the per-point GEMM and gather passes over it (csrc/edge_max.hip).
-    holder: bn; also receives last_sel, the selected ranks."""
+    holder: bn, double_backward, input_only; also receives last_sel, the selected ranks.
+    With holder.double_backward and a backward that is asked to build a graph, the first backward runs as a differentiable node
+    (EdgeMaxConvBwdFn); otherwise the layer is once differentiable."""
 
     @staticmethod
     def forward(ctx, h, x, W, b, gamma, beta):
@@ -289,20 +292,32 @@ class EdgeMaxConvFn(Function):
             out_pm, sel = edge_max.edge_max_eval(PQ, idx, st[0], st[1])
         h.last_idx, h.last_sel = idx, sel
         ctx.h, ctx.st = h, st
-        ctx.save_for_backward(x, PQ, sel, idx, Wst)          # x, not its point-major copy: the input is alive anyway
+        # x, not its point-major copy: the input is alive anyway.  The opted-in layer also keeps W and gamma (inputs: no copy), which must
+        # reach the differentiable first backward as inputs of its node -- Wst is an image, not a leaf.
+        ctx.save_for_backward(x, PQ, sel, idx, Wst, *((W, gamma) if getattr(h, "double_backward", False) else ()))
         return ops.pm_to_cm(out_pm, B, N)
 
     @staticmethod
     def backward(ctx, dout):
+        if getattr(ctx.h, "double_backward", False) and torch.is_grad_enabled():
+            x, PQ, sel, idx, Wst, W, gamma = ctx.saved_tensors
+            need = tuple(ctx.needs_input_grad)
+            if getattr(ctx.h, "input_only", False):              # the penalty consumes dx alone
+                need = need[:2] + (False,) * 4
+            return (None,) + EdgeMaxConvBwdFn.apply(ctx.h, ctx.st, need, dout, x, W, gamma, PQ, sel, idx, Wst)
         refuse_double_backward("edgeConv")
         return EdgeMaxConvFn._backward(ctx, dout)
 
     @staticmethod
     @once_differentiable
     def _backward(ctx, dout):
-        x, PQ, sel, idx, Wst = ctx.saved_tensors
-        h = ctx.h
-        scale, _, invstd, mean = ctx.st
+        x, PQ, sel, idx, Wst = ctx.saved_tensors[:5]
+        return (None,) + EdgeMaxConvFn.first_backward(ctx.h, ctx.st, ctx.needs_input_grad, dout, x, PQ, sel, idx, Wst, False)[0]
+
+    @staticmethod
+    def first_backward(h, st, need, dout, x, PQ, sel, idx, Wst, keep: bool):
+        """-> ((dx, dW, db, dgamma, dbeta), keep ? (r, sums, dPQ, rowptr, src) : None); need = needs_input_grad of (h, x, W, b, gamma, beta)"""
+        scale, _, invstd, mean = st
         F_ = sel.shape[1]
         r = ops.cm_to_pm(dout)                                           # a fresh [M,F] tensor: overwritten with g * 1[out > 0]
         sums = edge_max.edge_max_bwd_point(r, sel, PQ, idx, mean, invstd)
@@ -311,13 +326,79 @@ class EdgeMaxConvFn(Function):
             dPQ = edge_max.edge_max_bwd_graph(r, sel, PQ, h.k, rowptr, src, scale, idx, mean, invstd, sums)
         else:
             dPQ = edge_max.edge_max_bwd_graph(r, sel, PQ, h.k, rowptr, src, scale)
+        kept = (r, sums, dPQ, rowptr, src) if keep else None
         del r
-        need = ctx.needs_input_grad
         # dW first: its split-K workspace and the point rows die before dx is made
         dW = unstacked_grad(ops.gemm_tn(dPQ, ops.cm_to_pm(x))) if need[2] else None
         dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wst.t().contiguous()), h.B, h.N) if need[1] else None
         db = dbias(dPQ[:, F_:], h.training) if need[3] else None
-        return (None, dx, dW, db) + gb(sums, need, 4)
+        return (dx, dW, db) + gb(sums, need, 4), kept
+
+
+class EdgeMaxConvBwdFn(Function):
+    """EdgeMaxConvFn's first backward as a differentiable node: (dout, x, W, gamma) -> (dx, dW, db, dgamma, dbeta), the same launches in
+    the same order as the plain backward.  Its own backward is the closed-form second derivative THROUGH dx: for the
+    cotangent v of dx, one more per-point GEMM VPQ = v Wst^T, the two dbl passes of csrc/edge_max.hip -- the direction's edge sums, then the
+    cotangents of the incoming cotangent (ghat) and of PQ (PQbar) --, xbar = PQbar Wst and Wstbar = PQbar^T x + dPQ^T v; no per-edge tensor.
+    Eval mode (statistics constant): no PQbar, no xbar.  A cotangent on dW, db, dgamma or dbeta is refused (NotImplementedError); a third
+    derivative is refused like every second one of this family (RuntimeError).
+    Kept between the two backwards: r [M,F], dPQ [M,2F] (kept, not recomputed: DESIGN.md section 27), the [2F] sums and the reverse CSR."""
+
+    OUTPUTS = ("dx", "dW (conv.conv.weight)", "db (conv.conv.bias)", "dgamma (conv.bn.weight)", "dbeta (conv.bn.bias)")
+
+    @staticmethod
+    def forward(ctx, h, st, need, dout, x, W, gamma, PQ, sel, idx, Wst):
+        grads, (r, sums, dPQ, rowptr, src) = EdgeMaxConvFn.first_backward(h, st, need, dout, x, PQ, sel, idx, Wst, True)
+        ctx.h, ctx.st = h, st
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, PQ, sel, idx, Wst, r, sums, dPQ, rowptr, src)
+        return grads
+
+    @staticmethod
+    def backward(ctx, *cot):
+        if torch.is_grad_enabled():
+            raise RuntimeError("edgeConv(double_backward=True) is twice differentiable: its double backward was asked to build a graph "
+                               "(create_graph=True), but it has no third derivative")
+        for name, c in zip(EdgeMaxConvBwdFn.OUTPUTS[1:], cot[1:]):
+            if c is not None:
+                raise NotImplementedError("edgeConv(double_backward=True): a cotangent arrived on %s of the first backward; only second "
+                                          "derivatives through dx are served (gradient penalties, R1)" % name)
+        if cot[0] is None:
+            return (None,) * 11
+        return EdgeMaxConvBwdFn._backward(ctx, cot[0])
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, v):
+        x, PQ, sel, idx, Wst, r, sums, dPQ, rowptr, src = ctx.saved_tensors
+        h = ctx.h
+        scale, _, invstd, mean = ctx.st
+        F_ = sel.shape[1]
+        E = float(idx.numel())
+        need = ctx.needs_input_grad                                      # (h, st, need, dout, x, W, gamma, ...)
+        v_pm = ops.cm_to_pm(v)
+        VPQ = ops.gemm_nt(v_pm, Wst)                                     # [VP | VQ]: no bias
+        if h.training:
+            dsums = edge_max.edge_max_dbl_point(r, sel, PQ, VPQ, idx, mean, invstd)
+            ghat, PQbar = edge_max.edge_max_dbl_graph(r, sel, PQ, VPQ, idx, scale, h.k, rowptr, src, mean, invstd, sums, dsums)
+            T1, T2, S = dsums[:F_], dsums[F_:2 * F_], dsums[2 * F_:]
+            A = S - sums[:F_] * T1 / E - sums[F_:] * T2 / E
+        else:
+            A = edge_max.edge_max_dbl_point(r, sel, PQ, VPQ, idx)
+            ghat, PQbar = edge_max.edge_max_dbl_graph(r, sel, PQ, VPQ, idx, scale, h.k)
+        del VPQ
+        dgamma = invstd * A if need[6] else None
+        dW = None
+        if need[5]:
+            if PQbar is not None:
+                dWst = ops.gemm_tn(PQbar, ops.cm_to_pm(x))
+                ops.gemm_tn(dPQ, v_pm, out=dWst, beta=1.0)
+            else:
+                dWst = ops.gemm_tn(dPQ, v_pm)
+            dW = unstacked_grad(dWst)
+        dx = ops.pm_to_cm(ops.gemm_nt(PQbar, Wst.t().contiguous()), h.B, h.N) if (need[4] and PQbar is not None) else None
+        dg = ops.pm_to_cm(ghat, h.B, h.N) if need[3] else None
+        return (None, None, None, dg, dx, dW, dgamma) + (None,) * 4
 
 
 class UpsampleEdgeConvFn(Function):

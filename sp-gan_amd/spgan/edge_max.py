@@ -21,10 +21,11 @@ def _pq(PQ: Tensor, F_: int) -> Tensor:
     return PQ
 
 
-def tile_sums(part: Tensor, M_: int, tile_points: int) -> Tensor:
-    """A backward pass's per-tile records, partials [tiles,F,2] over M points in tiles of tile_points -> sums [2F] = [sum | sum * xhat]"""
+def tile_sums(part: Tensor, M_: int, tile_points: int, out: Optional[Tensor] = None) -> Tensor:
+    """A backward pass's per-tile records, partials [tiles,F,2] over M points in tiles of tile_points -> sums [2F] = [sum | sum * xhat]
+    (into out [2,F] when given)"""
     tiles, F_ = part.shape[0], part.shape[1]
-    sums = torch.empty((2, F_), dtype=torch.float32, device=part.device)
+    sums = torch.empty((2, F_), dtype=torch.float32, device=part.device) if out is None else out
     check(_lib.load().spgan_colstats_finalize(_p(part), 1, tiles, F_, M_, 1, tile_points, _p(sums[0]), _p(sums[1]), _s()), "colstats_finalize")
     return sums.view(-1)
 
@@ -107,3 +108,63 @@ def edge_max_bwd_graph(r: Tensor, sel: Tensor, PQ: Tensor, k: int, rowptr: Tenso
                                                _p(_vec(mean, F_, "mean")), _p(_vec(invstd, F_, "invstd")), _p(_vec(sums, 2 * F_, "sums")), _p(dPQ),
                                                2 * F_, _s()), "edge_max_bwd_graph", M=M_, k=k, F=F_)
     return dPQ
+
+
+def _vpq(VPQ: Tensor, PQ: Tensor) -> Tensor:
+    _f32(VPQ, "VPQ", 2)
+    if not VPQ.is_contiguous() or VPQ.shape != PQ.shape:
+        raise ValueError("VPQ must be contiguous [M, 2F] like PQ")
+    return VPQ
+
+
+def _r_sel(r: Tensor, sel: Tensor) -> None:
+    _f32(r, "r", 2)
+    if not r.is_contiguous() or sel.dtype != torch.uint8 or not sel.is_contiguous() or sel.shape != r.shape:
+        raise ValueError("r must be contiguous [M,F] and sel uint8 of the same shape")
+
+
+def edge_max_dbl_point(r: Tensor, sel: Tensor, PQ: Tensor, VPQ: Tensor, idx: Tensor, mean: Optional[Tensor] = None,
+                       invstd: Optional[Tensor] = None) -> Tensor:
+    """The direction's sums for the second derivative through dx: VPQ [M,2F] = [VP | VQ] = v Wst^T, t(i,j) = VQ_i + VP_n(i,j).
+    With mean, invstd (train mode) -> dsums [3F] = [T1 | T2 | S] = [sum_e t_e | sum_e t_e * xhat_e | sum_i r_i * t(i, sel)];
+    without (eval mode) -> [F] = S."""
+    M_, F_ = r.shape
+    _pq(PQ, F_); _vpq(VPQ, PQ); _i32(idx, "idx"); _r_sel(r, sel)
+    train = mean is not None
+    lib = _lib.load()
+    tp = lib.spgan_edge_max_tile_points()
+    part = torch.empty((2 if train else 1, (M_ + tp - 1) // tp, F_, 2), dtype=torch.float32, device=r.device)
+    check(lib.spgan_edge_max_dbl_point(_p(r), _p(sel), _p(PQ), 2 * F_, _p(VPQ), 2 * F_, _p(idx), M_, idx.shape[1], F_, _p(_vec(mean, F_, "mean")),
+                                       _p(_vec(invstd, F_, "invstd")), _p(part[0]) if train else None, _p(part[-1]), _s()),
+          "edge_max_dbl_point", M=M_, F=F_)
+    dsums = torch.empty((4 if train else 2, F_), dtype=torch.float32, device=r.device)
+    if train:
+        tile_sums(part[0], M_, tp, out=dsums[:2])
+    tile_sums(part[-1], M_, tp, out=dsums[-2:])
+    return dsums.view(-1)[:3 * F_] if train else dsums[0]
+
+
+def edge_max_dbl_graph(r: Tensor, sel: Tensor, PQ: Tensor, VPQ: Tensor, idx: Tensor, scale: Tensor, k: Optional[int] = None,
+                       rowptr: Optional[Tensor] = None, src: Optional[Tensor] = None, mean: Optional[Tensor] = None,
+                       invstd: Optional[Tensor] = None, sums: Optional[Tensor] = None, dsums: Optional[Tensor] = None):
+    """-> (ghat [M,F], PQbar [M,2F] | None): the cotangents of the incoming cotangent g and of PQ.  sums, dsums (with rowptr, src, mean,
+    invstd): train mode; without: eval mode (the statistics are constants: ghat = 1[out > 0] * scale * t(i, sel), no PQbar)."""
+    M_, F_ = r.shape
+    _pq(PQ, F_); _vpq(VPQ, PQ); _i32(idx, "idx"); _r_sel(r, sel)
+    k = idx.shape[1] if k is None else k
+    if idx.shape != (M_, k):
+        raise ValueError("idx [M,k] does not fit r [M,F]")
+    train = sums is not None
+    ghat = torch.empty((M_, F_), dtype=torch.float32, device=r.device)
+    PQbar = None
+    if train:
+        _i32(rowptr, "rowptr"); _i32(src, "src")
+        if rowptr.numel() != M_ + 1 or src.numel() != M_ * k:
+            raise ValueError("rowptr [M+1] / src [M*k] do not fit r [M,F]")
+        PQbar = torch.empty((M_, 2 * F_), dtype=torch.float32, device=r.device)
+    check(_lib.load().spgan_edge_max_dbl_graph(_p(r), _p(sel), _p(PQ), 2 * F_, _p(VPQ), 2 * F_, _p(rowptr) if train else None,
+                                               _p(src) if train else None, _p(idx), M_, k, F_, _p(_vec(scale, F_, "scale")),
+                                               _p(_vec(mean, F_, "mean")) if train else None, _p(_vec(invstd, F_, "invstd")) if train else None,
+                                               _p(_vec(sums, 2 * F_, "sums")), _p(_vec(dsums, 3 * F_, "dsums")), _p(ghat), _p(PQbar), 2 * F_, _s()),
+          "edge_max_dbl_graph", M=M_, k=k, F=F_)
+    return ghat, PQbar

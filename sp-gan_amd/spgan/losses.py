@@ -151,7 +151,11 @@ class GradientPenalty:
     """WGAN-GP penalty, Common/gradient_penalty.py:4-37:
         alpha ~ U[0,1] per sample; x_hat = real + alpha*(fake-real); g = d netD(x_hat)/d x_hat (create_graph);
         penalty = lambdaGP * mean(((||g_b||_2 - gamma)/gamma)^2).
-    `netD` must be an spgan.Discriminator (its input-gradient node is differentiable once more).
+    `netD` is any module whose input gradient is differentiable once more: an spgan.Discriminator, or a critic composed of
+    spgan.edgeConv(..., double_backward=True) layers and ordinary torch ops (a DGCNN-style critic).  The other gather-side edge
+    convolutions are once differentiable and raise under the penalty.  netD runs inside functions.input_grad_only(): the nodes it
+    builds deliver d netD / d x_hat as a differentiable tensor and skip the first-order parameter gradients, which the penalty never
+    consumes.
 
     The second GradientPenalty of the reference (Common/loss_utils.py:1087-1131) differs in two ways, both available here:
     `mix="loss_utils"` interpolates alpha*real + (1-alpha)*fake (:1108), and `mapping=True` (:1110-1118) first pairs every fake point

@@ -665,13 +665,24 @@ class edgeConv(nn.Module):
     point (edge_conv.EdgeMaxConvFn): no [B,2Fin,N,k] tensor in forward or backward.  idx (an extension): the graph to use instead of the kNN
     graph of x, int64 [B, N*k] local indices as get_edge_features returns them (or int32 [B*N,k] global rows: the layer's own format, trusted -- only
     int64 graphs are range-checked).  A negative bn.weight
-    entry takes the min branch.  Once differentiable.  last_idx / last_sel: the graph and the selected ranks of the latest forward."""
+    entry takes the min branch.  last_idx / last_sel: the graph and the selected ranks of the latest forward.
+    double_backward (an extension, and a plain attribute; not part of the state_dict): False -- the default -- leaves the layer once
+    differentiable: a backward asked to build a graph (create_graph=True) raises.  True makes the input gradient differentiable once
+    more (edge_conv.EdgeMaxConvBwdFn): torch.autograd.grad(out, x, create_graph=True) returns a dx with a graph whose
+    backward delivers gradients for x (train mode; None in eval mode, where the statistics are constants), conv.conv.weight,
+    conv.bn.weight and the incoming cotangent (which chains stacked layers); conv.conv.bias and conv.bn.bias have no second derivative
+    (None).  That is what a gradient penalty needs (spgan.GradientPenalty, R1); only second derivatives THROUGH dx are served: a cotangent
+    on the first backward's parameter gradients raises NotImplementedError, and a third derivative raises RuntimeError.  Without
+    create_graph the same launches run in the same order as in the default layer.  Inside functions.input_grad_only() (GradientPenalty's
+    forward) the differentiable first backward skips the parameter gradients (dW, db, dgamma, dbeta), which the penalty never consumes, and
+    returns None for them."""
 
-    def __init__(self, Fin, Fout, k):
+    def __init__(self, Fin, Fout, k, double_backward: bool = False):
         super().__init__()
         if not 1 <= k <= 127:
             raise ValueError("edgeConv: k must lie in 1..127")
         self.k = k
+        self.double_backward = bool(double_backward)
         self.Fin = Fin
         self.Fout = Fout
         self.conv = conv2dbr(2 * Fin, Fout, 1)
@@ -681,7 +692,8 @@ class edgeConv(nn.Module):
     def forward(self, x, idx: Optional[torch.Tensor] = None):
         bn = self.conv.bn
         B, N, idx, knn_mode = check_edge_input("edgeConv", x, idx, self.k, self.Fin, self.Fout, (bn,))
-        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=knn_mode, bn=bn, last_idx=None, last_sel=None)
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=knn_mode, bn=bn, last_idx=None, last_sel=None,
+                    double_backward=bool(self.double_backward), input_only=Fn._mode("input_only"))
         out = edge_conv.EdgeMaxConvFn.apply(h, x.contiguous(), self.conv.conv.weight, self.conv.conv.bias, bn.weight, bn.bias)
         self.last_idx, self.last_sel = h.last_idx, h.last_sel
         return out
