@@ -1155,6 +1155,26 @@ int spgan_pair_attn_bwd(int role, const float* pos, const float* Wp1p, const flo
                         const float* WcT, const float* wa2, const float* P, const float* dS, const float* dR, int b, int n, int Mp,
                         int Hp, float* dA, float* Z, void* ws, size_t ws_bytes, spgan_stream_t s);
 
+/* ------------------------------------------------------------------------------------------
+ * Dot-product point self-attention without a [b,n,n] map (csrc/point_attn.hip): per shape, on point-major rows,
+ *   S_ij = q_i . k_j (unscaled),  P = softmax_j(S),  O_i = sum_j P_ij v_j,  lse_i = log sum_j exp(S_ij).
+ * q, k [b*n,dk], v, o, dO [b*n,dv] with row strides ld* (column slices of one projected tensor are fine).  dk = a multiple of 4 up to 128
+ * (spgan_point_attn_padded_dk: the host pads with zero columns, which leaves S unchanged; 0 = outside the domain), dv = a multiple of 4 up
+ * to spgan_point_attn_max_dv(); every row stride a multiple of 4 and every base pointer 16-byte aligned.  Any b in 1..65535, any n >= 1.
+ * Exact fp32 MFMA; every sum has a fixed order (no float atomics).
+ * ---------------------------------------------------------------------------------------- */
+int spgan_point_attn_padded_dk(int dk);
+int spgan_point_attn_max_dv(void);
+/* online softmax over key tiles -> o [b*n,dv], lse [b*n]; nothing of size n^2 is written */
+int spgan_point_attn_fwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int b, int n, int dk, int dv, float* o,
+                         int ldo, float* lse, spgan_stream_t s);
+/* The backward recomputes P = exp(S - lse); dS = P (dO V^T - D), D_i = dO_i . o_i.  The workspace is lse and D [b*n].
+ * role 0 (query-stationary): writes D_i = sum_j P_ij (dO_i . v_j) / sum_j P_ij, then dq_i = sum_j dS_ij k_j [b*n,dk]; dkey / dval are unused.
+ * role 1 (key-stationary), after role 0: dval_j = sum_i P_ij dO_i [b*n,dv], dkey_j = sum_i dS_ij q_i [b*n,dk]; dq is unused. */
+int spgan_point_attn_bwd(int role, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* dO, int lddo,
+                         const float* lse, float* D, int b, int n, int dk, int dv, float* dq, int lddq, float* dkey, int lddk,
+                         float* dval, int lddv, spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

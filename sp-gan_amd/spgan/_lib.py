@@ -374,6 +374,10 @@ SIGNATURES = {
     "spgan_pair_attn_bwd_records": (I, [I, I]),
     "spgan_pair_attn_bwd_ws_bytes": (SZ, [I, I, I, I]),
     "spgan_pair_attn_bwd": (I, [I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, SZ, P]),
+    "spgan_point_attn_padded_dk": (I, [I]),
+    "spgan_point_attn_max_dv": (I, []),
+    "spgan_point_attn_fwd": (I, [P, I, P, I, P, I, I, I, I, I, P, I, P, P]),
+    "spgan_point_attn_bwd": (I, [I, P, I, P, I, P, I, P, I, P, P, I, I, I, I, P, I, P, I, P, I, P]),
 }
 
 _lib = None

@@ -736,7 +736,7 @@ class AttentionFn(Function):
     def forward(ctx, holder, x, *params):
         _record_modes(ctx, holder)
         P = dict(zip(ATTN_NAMES, params))
-        y, actx = nets.attention_forward(P, "attn", x.contiguous(), holder.B, holder.N)
+        y, actx = nets.attention_forward(P, "attn", x.contiguous(), holder.B, holder.N, materialize=getattr(holder, "materialize", True))
         ctx.actx = actx
         ctx.save_for_backward(*params)
         return y

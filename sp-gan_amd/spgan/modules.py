@@ -64,22 +64,75 @@ class EqualLinear(_EqualLR):
 
 
 class Attention(nn.Module):
-    """Generation/modules.py:534-558: non-local block over the points of a shape.  forward(x [B,ch,N]) -> [B,ch,N]."""
+    """Generation/modules.py:534-558: non-local block over the points of a shape.  forward(x [B,ch,N]) -> [B,ch,N].
+    materialize=True (the default) writes the [B,N,N] attention map and keeps it for the backward.  materialize=False (the argument,
+    or the attribute set afterwards) runs spgan.point_attn's online softmax instead: memory O(B N ch), no map; it
+    serves ch // 8 <= 128 and ch // 2 <= 512 (ValueError otherwise).  The parameters and the state_dict are the same either way."""
 
-    def __init__(self, ch: int, name: str = "attention"):
+    def __init__(self, ch: int, name: str = "attention", materialize: bool = True):
         super().__init__()
         self.ch = ch
+        self.materialize = bool(materialize)
+        if not self.materialize:
+            self._check_fused_domain()
         self.theta = nn.Conv1d(ch, ch // 8, 1, bias=False)
         self.phi = nn.Conv1d(ch, ch // 8, 1, bias=False)
         self.g = nn.Conv1d(ch, ch // 2, 1, bias=False)
         self.o = nn.Conv1d(ch // 2, ch, 1, bias=False)
         self.gamma = nn.Parameter(torch.tensor(0.), requires_grad=True)
 
+    def _check_fused_domain(self):
+        from . import point_attn
+        try:
+            point_attn.padded_dk(self.ch // 8)
+            point_attn.padded_dv(self.ch // 2)
+        except ValueError as e:
+            raise ValueError("Attention(ch=%d, materialize=False): %s" % (self.ch, e)) from None
+
     def forward_pm(self, x_pm, B: int, N: int):
-        return Fn.AttentionFn.apply(_Holder(B=B, N=N), x_pm, self.theta.weight, self.phi.weight, self.g.weight, self.o.weight, self.gamma)
+        if not self.materialize:
+            self._check_fused_domain()
+        return Fn.AttentionFn.apply(_Holder(B=B, N=N, materialize=bool(self.materialize)), x_pm, self.theta.weight, self.phi.weight,
+                                    self.g.weight, self.o.weight, self.gamma)
 
     def forward(self, x, y=None):
         _require_gpu(x, "Attention")
+        B, C, N = x.shape
+        return Fn.PmToCm.apply(self.forward_pm(Fn.CmToPm.apply(x), B, N), B, N)
+
+
+class Self_Attn(nn.Module):
+    """Common/utilities.py:210-245: the SAGAN block over the points of a shape.  forward(x [B,C,N]) -> [B,C,N] = gamma * attn + x with
+    out[:, :, j] = sum_i softmax_i(query_i . key_j) value_i: the reference normalises over the FIRST point index (softmax(query_key, 1))
+    and sums over it, so `key` plays the attending side.  query / key / value are nn.Conv1d with bias, in the reference's order:
+    state_dicts load strictly both ways.  Runs on spgan.point_attn (no [B,N,N] map); in_dim in 8..512 (ValueError otherwise), and
+    B * N * C a multiple of 4.  Differentiable once in x and every parameter.  `activation` is stored and unused, as in the reference."""
+
+    def __init__(self, in_dim: int = 128, activation: str = "relu"):
+        super().__init__()
+        from . import point_attn
+        in_dim = int(in_dim)
+        try:
+            point_attn.padded_dk(in_dim // 8)
+            point_attn.padded_dv(in_dim)
+        except ValueError as e:
+            raise ValueError("Self_Attn(in_dim=%d): %s" % (in_dim, e)) from None
+        self.chanel_in = in_dim
+        self.activation = activation
+        self.query = nn.Conv1d(in_channels=in_dim, out_channels=in_dim // 8, kernel_size=1)
+        self.key = nn.Conv1d(in_channels=in_dim, out_channels=in_dim // 8, kernel_size=1)
+        self.value = nn.Conv1d(in_channels=in_dim, out_channels=in_dim, kernel_size=1)
+        self.gamma = nn.Parameter(torch.zeros(1))
+
+    def forward_pm(self, x_pm, B: int, N: int):
+        from . import point_attn
+        return point_attn.SelfAttnFn.apply(_Holder(B=B, N=N), x_pm, self.query.weight, self.query.bias, self.key.weight, self.key.bias,
+                                           self.value.weight, self.value.bias, self.gamma)
+
+    def forward(self, x):
+        _require_gpu(x, "Self_Attn")
+        if x.dim() != 3 or x.shape[1] != self.chanel_in:
+            raise ValueError("Self_Attn: x must be [B,%d,N], got %s" % (self.chanel_in, tuple(x.shape)))
         B, C, N = x.shape
         return Fn.PmToCm.apply(self.forward_pm(Fn.CmToPm.apply(x), B, N), B, N)
 

@@ -1324,11 +1324,21 @@ def g_pair_forward(Ph, Pa1, Pe2, bufs_e2, Pa2, Pgt, bufs_g, x_pm2: Tensor, zb2: 
                 x1_in=a1[M:], a2=a2[M:])
 
 
-def attention_forward(P, pre: str, x: Tensor, B: int, N: int):
+def attention_forward(P, pre: str, x: Tensor, B: int, N: int, materialize: bool = True):
     """`Attention.forward` (Generation/modules.py:549-558) on point-major rows: x [M,C] -> gamma * W_o(beta g) + x with
     beta_b = softmax_rows(theta_b phi_b^T) per shape.  The [B,N,N] maps are materialised (537 MB at B=32, N=2048: they are kept
-    for the backward pass anyway); the per-shape products are ONE batched gemm_nt launch each (blockIdx.y = shape)."""
+    for the backward pass anyway); the per-shape products are ONE batched gemm_nt launch each (blockIdx.y = shape).
+    materialize=False: beta never exists -- one stacked projection [theta | phi | g] and spgan.point_attn's online softmax
+    (DESIGN 28); the context then holds x, the projection, o, oo and the log-sum-exp per point."""
     Wt, Wp, Wg, Wo = (_w2(P[pre + n + ".weight"]) for n in (".theta", ".phi", ".g", ".o"))
+    if not materialize:
+        from . import point_attn
+        Wcat, dims = point_attn.stacked_weight(Wt, Wp, Wg)
+        o_full, cat, lse = point_attn.projected_forward(x, Wcat, None, dims, B, N)
+        o = o_full if o_full.shape[1] == dims[2] else o_full[:, :dims[2]].contiguous()
+        oo = ops.gemm_nt(o, Wo)
+        y = ops.scale_residual(oo, x, P[pre + ".gamma"])
+        return y, dict(x=x, cat=cat, o=o, oo=oo, lse=lse, Wcat=Wcat, dims=dims, B=B, N=N)
     M = x.shape[0]
     theta, phi, gv = ops.gemm_nt(x, Wt), ops.gemm_nt(x, Wp), ops.gemm_nt(x, Wg)                  # [M,C/8], [M,C/8], [M,C/2]
     c8, c2 = theta.shape[1], gv.shape[1]
@@ -1344,12 +1354,26 @@ def attention_backward(P, pre: str, ctx, dy: Tensor, need_dx: bool = True):
     """-> (dx | None, {name: grad}).  dS = softmax'(dP), d theta = dS phi, d phi = dS^T theta, d g = beta^T d_o per shape; the two
     transposed products read explicitly transposed maps, so that all five are batched A.W^T launches."""
     Wt, Wp, Wg, Wo = (_w2(P[pre + n + ".weight"]) for n in (".theta", ".phi", ".g", ".o"))
-    x, theta, phi, gv, beta, o, B, N = (ctx[k] for k in ("x", "theta", "phi", "g", "beta", "o", "B", "N"))
+    x, theta, phi, gv, beta, o, B, N = (ctx.get(k) for k in ("x", "theta", "phi", "g", "beta", "o", "B", "N"))
     dy = dy.contiguous()
     g: Dict[str, Tensor] = {}
     d_oo, g[pre + ".gamma"] = ops.scale_residual_bwd(dy, ctx["oo"], P[pre + ".gamma"])
     g[pre + ".o.weight"] = ops.gemm_tn(d_oo, o, defer=True).view_as(P[pre + ".o.weight"])
     d_o = ops.gemm_nt(d_oo, _t(Wo))                                                              # [M,C/2]
+    if "lse" in ctx:                                                                             # materialize=False: beta recomputed per tile
+        from . import point_attn
+        c8, dkp, c2, dvp = ctx["dims"]
+        if dvp != c2:
+            d_o = torch.nn.functional.pad(d_o, (0, dvp - c2))
+        dcat = point_attn.projected_backward(ctx["cat"], ctx["lse"], d_o, ctx["dims"], B, N)   # [d theta | d phi | d g]
+        dW = ops.gemm_tn(dcat, x, defer=True)
+        for n, lo, w in ((".theta", 0, c8), (".phi", dkp, c8), (".g", 2 * dkp, c2)):
+            g[pre + n + ".weight"] = dW[lo:lo + w].reshape(P[pre + n + ".weight"].shape)
+        dx = None
+        if need_dx:
+            dx = ops.gemm_nt(dcat, _t(ctx["Wcat"]))
+            ops.multi_add([dx], [dy])
+        return dx, g
     c8, c2 = theta.shape[1], gv.shape[1]
     dcat = torch.empty((x.shape[0], 2 * c8 + c2), dtype=torch.float32, device=x.device)         # [d theta | d phi | d g]
     dcat3 = dcat.view(B, N, 2 * c8 + c2)
