@@ -1175,6 +1175,32 @@ int spgan_point_attn_bwd(int role, const float* q, int ldq, const float* k, int 
                          const float* lse, float* D, int b, int n, int dk, int dv, float* dq, int lddq, float* dkey, int lddk,
                          float* dval, int lddv, spgan_stream_t s);
 
+/* Dense edge / point layers (csrc/edge_dense.hip): DenseEdgeModule and DenseModule1D of Common/utilities.py:22-42, 123-144 without the
+ * concatenated tensors.  Exact fp32 MFMA products; no float atomics: results repeat bit for bit.
+ *   spgan_edge_dense_level:    Y[m, n] = sum_{c < K} op(A)[m, c] * W[n, c] + bias[n] + Q[m / k, n] + P[idx[m], n], m < M, n < N.
+ *                              op(A)[m, c] = A[m*lda + c] for c < raw_cols and lrelu(A[m*lda + c]*scale[c] + shift[c], slope) for
+ *                              raw_cols <= c < K (scale, shift [K]; entries below raw_cols are not read; both may be NULL with raw_cols == K):
+ *                              A is the virtual concatenation [raw input | stored pre-norm blocks], each block activated while it is staged.
+ *                              The addend is optional (PQ == NULL: none): P = columns [0, N) and Q = columns [qoff, qoff + N) of PQ [M/k, ldpq],
+ *                              idx [M] int32 rows of PQ (an entry outside [0, M/k) reads the row's own point), M % k == 0.  bias optional.
+ *                              Y [M, ldy >= N] may be a column slice of the buffer A is read from: the columns written and the K columns
+ *                              read must be DISJOINT (nothing orders a workgroup's stores against another's loads).
+ *                              partials (optional) [ceil(M / tile_rows)][N][2] = (sum, centred M2) of Y per row tile: the records
+ *                              spgan_colstats_finalize / _finalize_bn read (mode 0, tile_rows = spgan_edge_dense_tile_rows()).
+ *                              Any M, N >= 1, K >= 0 (K == 0: the addend / bias alone, a gather into a strided slice); tails in the kernel.
+ *   spgan_edge_dense_scatter:  D [M*k, ldd >= C] on the edges -> dPQ [M, ldo >= 2C] = [dP | dQ]: dQ[i] = sum over the k rows of point i,
+ *                              dP[j] = sum of D[e] over the in-edge list of j (spgan_csr_build, ascending edge ids; in-degree 0: zeros).
+ *   spgan_edge_dense_bn_apply: spgan_bn_bwd_apply with a row stride per tensor: dz[m*ldd + c] = gamma*invstd*(g[m*ldg + c] - sums[c]/count
+ *                              - xhat*sums[C + c]/count), xhat = (z[m*ldz + c] - mean)*invstd; dz must not alias g or z. */
+int spgan_edge_dense_tile_rows(void);
+int spgan_edge_dense_level(const float* A, int lda, int raw_cols, const float* scale, const float* shift, float slope, const float* W, int ldw,
+                           const float* bias, const float* PQ, int ldpq, int qoff, const int32_t* idx, int k, int M, int N, int K, float* Y,
+                           int ldy, float* partials, spgan_stream_t s);
+int spgan_edge_dense_scatter(const float* D, int ldd, const int32_t* rowptr, const int32_t* src, int M, int k, int C, float* dPQ, int ldo,
+                             spgan_stream_t s);
+int spgan_edge_dense_bn_apply(const float* g, int ldg, const float* z, int ldz, int M, int C, const float* mean, const float* invstd,
+                              const float* gamma, const float* sums, int count, float* dz, int ldd, spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

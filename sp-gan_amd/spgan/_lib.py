@@ -378,6 +378,10 @@ SIGNATURES = {
     "spgan_point_attn_max_dv": (I, []),
     "spgan_point_attn_fwd": (I, [P, I, P, I, P, I, I, I, I, I, P, I, P, P]),
     "spgan_point_attn_bwd": (I, [I, P, I, P, I, P, I, P, I, P, P, I, I, I, I, P, I, P, I, P, I, P]),
+    "spgan_edge_dense_tile_rows": (I, []),
+    "spgan_edge_dense_level": (I, [P, I, I, P, P, F, P, I, P, P, I, I, P, I, I, I, I, P, I, P, P]),
+    "spgan_edge_dense_scatter": (I, [P, I, P, P, I, I, I, P, I, P]),
+    "spgan_edge_dense_bn_apply": (I, [P, I, P, I, I, I, P, P, P, P, I, P, I, P]),
 }
 
 _lib = None

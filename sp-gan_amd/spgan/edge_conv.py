@@ -26,14 +26,14 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import block_tail, edge_max, edge_rank, edge_weight, edge_window, ops
+from . import block_tail, edge_dense, edge_max, edge_rank, edge_weight, edge_window, ops
 
 Tensor = torch.Tensor
 
 
 # ----------------------------------------------------------------------------- operand images
 # one dictionary per builder: a layer that reaches the cap does not evict another layer's images
-_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}, "coord": {}, "bilateral": {}, "tail": {}}
+_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}, "coord": {}, "bilateral": {}, "tail": {}, "dense_edge": {}, "dense_rows": {}}
 
 
 def cached_images(cache: Dict[tuple, tuple], weights: Sequence[Tensor], extra: tuple, build: Callable):
@@ -194,6 +194,44 @@ def bilateral_images(W1: Tensor, Wf: Tensor, Wx: Tensor, Wa2: Tensor, Wa3: Tenso
                 Wst_x.t().contiguous(), torch.cat([Wc1, Wst_f], dim=0).t().contiguous(), Wm2.contiguous(), Wm2.t().contiguous(), Wm3.contiguous(),
                 Wm3.t().contiguous())
     return cached_images(_IMAGES["bilateral"], (W1, Wf, Wx, Wa2, Wa3, V), (C, k), build)
+
+
+def dense_edge_images(Ws: Sequence[Tensor], C: int):
+    """The operand images of DenseEdgeModule's L conv weights (W_l [G, 2C + (l-1)G, 1, 1] over cat[x_j - x_i, x_i, y_1 .. y_{l-1}], l = 1..L):
+    (Wst [2LG, C] = rows of P_1 .. P_L, then of Q_1 .. Q_L with P_l = W_l[:, :C] (the difference half comes FIRST here: the other way
+    round from `stacked`) and Q_l = W_l[:, C:2C] - W_l[:, :C]; Wst^T; Wy = the y columns W_l[:, 2C:] [G, (l-1)G] of l = 2..L; Wback =
+    per m = 1..L-1 the stack [G, (L-m)G] of the transposed y_m columns of every later level, the operand of gy_m = D[:, mG:] . Wback_m^T).
+    Cached per weight set (cached_images)."""
+    def build(*Ws):
+        L, G = len(Ws), Ws[0].shape[0]
+        Wm = [W.reshape(W.shape[0], W.shape[1]) for W in Ws]
+        Wst = torch.cat([w[:, :C] for w in Wm] + [w[:, C:2 * C] - w[:, :C] for w in Wm], dim=0).contiguous()
+        Wy = tuple(Wm[l][:, 2 * C:].contiguous() for l in range(1, L))
+        Wback = tuple(torch.cat([Wm[l][:, 2 * C + m * G:2 * C + (m + 1) * G].t() for l in range(m + 1, L)], dim=1).contiguous() for m in range(L - 1))
+        return Wst, Wst.t().contiguous(), Wy, Wback
+    return cached_images(_IMAGES["dense_edge"], tuple(Ws), (C,), build)
+
+
+def dense_edge_unstacked_grad(dWst: Tensor, l: int, L: int, G: int) -> Tensor:
+    """[2LG, C] (rows of dW'_P, then of dW'_Q) -> level l's gradient of the e0 columns [G, 2C]: dW[:, :C] = dW'_P - dW'_Q, dW[:, C:2C] = dW'_Q"""
+    dP, dQ = dWst[l * G:(l + 1) * G], dWst[(L + l) * G:(L + l + 1) * G]
+    return torch.cat([dP - dQ, dQ], dim=1)
+
+
+def dense_rows_images(Ws: Sequence[Tensor], Cin: int):
+    """The operand images of DenseModule1D's conv weights (W_l [w_l, Cin + off_l, 1] over cat[x, y_1 .. y_{l-1}], off_l = w_1 + .. + w_{l-1}):
+    (Wm = the weights as matrices; Wx_t [Cin, S] = the transposed x columns of every level side by side, S = sum w_l; Wback = per level
+    m < L the stack [w_m, S - off_{m+1}] of the transposed y_m columns of every later level).  Cached per weight set (cached_images)."""
+    def build(*Ws):
+        L = len(Ws)
+        Wm = [W.reshape(W.shape[0], W.shape[1]).contiguous() for W in Ws]
+        off = [0]
+        for w in Wm:
+            off.append(off[-1] + w.shape[0])
+        Wx_t = torch.cat([w[:, :Cin].t() for w in Wm], dim=1).contiguous()
+        Wback = tuple(torch.cat([Wm[l][:, Cin + off[m]:Cin + off[m + 1]].t() for l in range(m + 1, L)], dim=1).contiguous() for m in range(L - 1))
+        return tuple(Wm), Wx_t, Wback
+    return cached_images(_IMAGES["dense_rows"], tuple(Ws), (Cin,), build)
 
 
 # ----------------------------------------------------------------------------- what the Functions share
@@ -1016,3 +1054,188 @@ class BlockTailFn(Function):
         if not middle:
             dxs = dxs_t
         return (None, dY, dxs if need[2] else None, dg) + gb(sums, need, 4) + (dWa, dba, dga, dbea)
+
+
+DENSE_SLOPE = 0.2
+
+
+class DenseEdgeFn(Function):
+    """out [B,G,N] = max_j y_L(i,j), y_l = lrelu(bn_l(W_l . cat[e0, y_1 .. y_{l-1}] + b_l), 0.2), e0(i,j) = cat[x_j - x_i, x_i]   (the
+    reference's DenseEdgeModule, Common/utilities.py:123-144) without the [B,2C,N,k] edge tensor, any concatenation or any activated
+    per-edge tensor, forward or backward.  The e0 part of all levels is ONE per-point GEMM, PQ [M, 2LG] = [P_1 .. P_L | Q_1 .. Q_L]
+    (dense_edge_images); level l's pre-norm rows z_l go into column slice l of one buffer Z [E, LG], formed from the slices in front of
+    it -- activated while they are staged -- plus Q_l[i] + P_l[j] (csrc/edge_dense.hip), with the BatchNorm records from the same launch.
+    The backward holds D [E, LG] (the gradients reaching z_l, last level first: gy_m is ONE product over the finished slices behind m)
+    and one [E,G] buffer; D scatters to dPQ through the reverse CSR.
+    holder: B, N, k, training, idx, knn_mode, bns; parameters (W, b, gamma, beta) per level.  Saved: x, Z, the graph, the pooled result
+    and its arg-max, the per-column (scale, shift) and the statistics."""
+
+    @staticmethod
+    def forward(ctx, h, x, *params):
+        from . import pointnet_util
+        B, C, N = x.shape
+        L, k, M, train = len(h.bns), h.k, B * N, h.training
+        Ws, bs, gammas, betas = params[0::4], params[1::4], params[2::4], params[3::4]
+        G = Ws[0].shape[0]
+        E, LG = M * k, L * G
+        x_pm = ops.cm_to_pm(x)
+        idx = h.idx if h.idx is not None else dense_graph(x_pm, B, N, k, h.knn_mode)
+        Wst, _, Wy, _ = dense_edge_images(Ws, C)
+        # exact=True: fp32 operands whatever ops.set_mfma_operands selected
+        PQ = ops.gemm_nt(x_pm, Wst, torch.cat([torch.zeros_like(b) for b in bs] + [b.detach() for b in bs]), exact=True)
+        Z = torch.empty((E, LG), dtype=torch.float32, device=x.device)
+        SC = torch.empty((2, LG), dtype=torch.float32, device=x.device)      # (scale | shift) of every column of Z
+        sts = []
+        for l in range(L):
+            lo, hi = l * G, (l + 1) * G
+            res = edge_dense.edge_dense_level(Z[:, :lo] if l else None, Wy[l - 1] if l else None, Z[:, lo:hi], raw_cols=0, scale=SC[0, :lo],
+                                              shift=SC[1, :lo], slope=DENSE_SLOPE, addend=(PQ[:, lo:hi], PQ[:, LG + lo:LG + hi], idx), stats=train)
+            st = bn_stats(h.bns[l], train, E, gammas[l], betas[l], records=res[1:] if train else None)
+            SC[:, lo:hi] = st[:2]
+            sts.append(st)
+        del PQ
+        out_pm, arg = pointnet_util._group_max(Z[:, LG - G:], M, k, sts[-1][0], sts[-1][1], DENSE_SLOPE)
+        h.last_idx = idx
+        ctx.h, ctx.sts = h, sts
+        ctx.save_for_backward(x, Z, idx, out_pm, arg, SC, *Ws, *gammas)
+        return ops.pm_to_cm(out_pm, B, N)
+
+    @staticmethod
+    def backward(ctx, dout):
+        refuse_double_backward("DenseEdgeModule")
+        return DenseEdgeFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        from . import pointnet_util
+        h, sts = ctx.h, ctx.sts
+        L = len(sts)
+        x, Z, idx, out_pm, arg, SC = ctx.saved_tensors[:6]
+        Ws, gammas = ctx.saved_tensors[6:6 + L], ctx.saved_tensors[6 + L:]
+        B, C, N = x.shape
+        k, M, train = h.k, B * N, h.training
+        G = Ws[0].shape[0]
+        E, LG = M * k, L * G
+        need = ctx.needs_input_grad
+        _, Wst_t, _, Wback = dense_edge_images(Ws, C)
+        D = torch.empty((E, LG), dtype=torch.float32, device=x.device)
+        sums = [None] * L
+        _, _, inv, mu = sts[-1]
+        r, sums[-1] = pointnet_util._group_max_bwd(ops.cm_to_pm(dout), out_pm, arg, Z[:, LG - G:], mu, inv, DENSE_SLOPE, k)
+        edge_dense.edge_dense_bn_apply(r, Z[:, LG - G:], mu, inv, gammas[-1], used(sums[-1], train), E, D[:, LG - G:])
+        del r
+        for m in range(L - 2, -1, -1):
+            lo, hi = m * G, (m + 1) * G
+            sc, sh, inv, mu = sts[m]
+            # the LeakyReLU mask of z_m and the two BatchNorm sums come out of the product's epilogue
+            gz, t1, t2 = ops.gemm_nt_bnbwd(D[:, hi:], Wback[m], Z[:, lo:hi], sc, sh, mu, inv, DENSE_SLOPE, exact=True)
+            sums[m] = torch.cat([t1, t2])
+            edge_dense.edge_dense_bn_apply(gz, Z[:, lo:hi], mu, inv, gammas[m], used(sums[m], train), E, D[:, lo:hi])
+            del gz
+        rowptr, src = ops.csr_build(idx, B, N)
+        dPQ = edge_dense.edge_dense_scatter(D, rowptr, src, k)
+        del rowptr, src
+        dWst = ops.gemm_tn(dPQ, ops.cm_to_pm(x), exact=True) if any(need[2 + 4 * l] for l in range(L)) else None
+        grads = []
+        for l in range(L):
+            lo, hi = l * G, (l + 1) * G
+            dW = None
+            if need[2 + 4 * l]:
+                parts = [dense_edge_unstacked_grad(dWst, l, L, G)]
+                if l:
+                    parts.append(ops.gemm_tn(D[:, lo:hi], Z[:, :lo], pro=(SC[0, :lo], SC[1, :lo], DENSE_SLOPE), exact=True))
+                dW = torch.cat(parts, dim=1).view_as(Ws[l])
+            db = dbias(dPQ[:, LG + lo:LG + hi], train) if need[3 + 4 * l] else None
+            grads += [dW, db, *gb(sums[l], need, 4 + 4 * l)]
+        del D
+        dx = ops.pm_to_cm(ops.gemm_nt(dPQ, Wst_t, exact=True), B, N) if need[1] else None
+        return (None, dx, *grads)
+
+
+def dense_graph(x_pm: Tensor, B: int, N: int, k: int, knn_mode: int) -> Tensor:
+    """The reference's graph for the dense edge layers (Common/ops.py:129-135: topk of the negative squared distance, so the point itself
+    is a neighbour): idx int32 [M,k] = the point itself, then its k-1 nearest neighbours by ascending distance (ops.knn)"""
+    M = B * N
+    idx = torch.empty((M, k), dtype=torch.int32, device=x_pm.device)
+    idx[:, 0] = torch.arange(M, dtype=torch.int32, device=x_pm.device)
+    idx[:, 1:] = ops.knn(x_pm, B, N, k - 1, knn_mode)
+    return idx
+
+
+class DenseRowsFn(Function):
+    """out [B,Cin,N] = y_L, y_l = lrelu(bn_l(W_l . cat[x, y_1 .. y_{l-1}] + b_l), 0.2)   (the reference's DenseModule1D,
+    Common/utilities.py:22-42) without the concatenations or the activated tensors: one buffer R [M, Cin + S] = [x | z_1 | .. | z_L] of
+    the raw input and the pre-norm rows, each level a product over the columns in front of its slice with x taken as stored and the z
+    columns activated while they are staged (csrc/edge_dense.hip, raw_cols = Cin).  The backward mirrors DenseEdgeFn's with k = 1.
+    holder: B, N, training, bns; parameters (W, b, gamma, beta) per level."""
+
+    @staticmethod
+    def forward(ctx, h, x, *params):
+        from . import pointnet_util
+        B, Cin, N = x.shape
+        L, M, train = len(h.bns), B * N, h.training
+        Ws, bs, gammas, betas = params[0::4], params[1::4], params[2::4], params[3::4]
+        Wm, _, _ = dense_rows_images(Ws, Cin)
+        off = [Cin]
+        for w in Wm:
+            off.append(off[-1] + w.shape[0])
+        R = torch.empty((M, off[-1]), dtype=torch.float32, device=x.device)
+        pointnet_util._cm_to_rows(x.contiguous(), R, 0)
+        SC = torch.empty((2, off[-1]), dtype=torch.float32, device=x.device)  # (scale | shift) per column of R; the x columns are not read
+        sts = []
+        for l in range(L):
+            lo, hi = off[l], off[l + 1]
+            res = edge_dense.edge_dense_level(R[:, :lo], Wm[l], R[:, lo:hi], raw_cols=Cin, scale=SC[0, :lo], shift=SC[1, :lo], slope=DENSE_SLOPE,
+                                              bias=bs[l].detach(), stats=train)
+            st = bn_stats(h.bns[l], train, M, gammas[l], betas[l], records=res[1:] if train else None)
+            SC[:, lo:hi] = st[:2]
+            sts.append(st)
+        out_pm = ops.affine_act(R[:, off[-2]:], sts[-1][0], sts[-1][1], DENSE_SLOPE)
+        ctx.h, ctx.sts, ctx.off = h, sts, off
+        ctx.save_for_backward(R, out_pm, SC, *Ws, *gammas)
+        return ops.pm_to_cm(out_pm, B, N)
+
+    @staticmethod
+    def backward(ctx, dout):
+        refuse_double_backward("DenseModule1D")
+        return DenseRowsFn._backward(ctx, dout)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dout):
+        from . import pointnet_util
+        h, sts, off = ctx.h, ctx.sts, ctx.off
+        L = len(sts)
+        R, out_pm, SC = ctx.saved_tensors[:3]
+        Ws, gammas = ctx.saved_tensors[3:3 + L], ctx.saved_tensors[3 + L:]
+        M, Cin, train = R.shape[0], off[0], h.training
+        need = ctx.needs_input_grad
+        _, Wx_t, Wback = dense_rows_images(Ws, Cin)
+        D = torch.empty((M, off[-1] - Cin), dtype=torch.float32, device=R.device)      # column c of D belongs to column Cin + c of R
+        sums = [None] * L
+        _, _, inv, mu = sts[-1]
+        r, sums[-1] = pointnet_util._group_max_bwd(ops.cm_to_pm(dout), out_pm, None, R[:, off[-2]:], mu, inv, DENSE_SLOPE, 1)
+        edge_dense.edge_dense_bn_apply(r, R[:, off[-2]:], mu, inv, gammas[-1], used(sums[-1], train), M, D[:, off[-2] - Cin:])
+        del r
+        for m in range(L - 2, -1, -1):
+            lo, hi = off[m], off[m + 1]
+            sc, sh, inv, mu = sts[m]
+            gz, t1, t2 = ops.gemm_nt_bnbwd(D[:, hi - Cin:], Wback[m], R[:, lo:hi], sc, sh, mu, inv, DENSE_SLOPE, exact=True)
+            sums[m] = torch.cat([t1, t2])
+            edge_dense.edge_dense_bn_apply(gz, R[:, lo:hi], mu, inv, gammas[m], used(sums[m], train), M, D[:, lo - Cin:hi - Cin])
+            del gz
+        grads = []
+        for l in range(L):
+            lo, hi = off[l], off[l + 1]
+            Dl = D[:, lo - Cin:hi - Cin]
+            dW = None
+            if need[2 + 4 * l]:
+                parts = [ops.gemm_tn(Dl, R[:, :Cin], exact=True)]
+                if l:
+                    parts.append(ops.gemm_tn(Dl, R[:, Cin:lo], pro=(SC[0, Cin:lo], SC[1, Cin:lo], DENSE_SLOPE), exact=True))
+                dW = torch.cat(parts, dim=1).view_as(Ws[l])
+            db = dbias(Dl, train) if need[3 + 4 * l] else None
+            grads += [dW, db, *gb(sums[l], need, 4 + 4 * l)]
+        dx = ops.pm_to_cm(ops.gemm_nt(D, Wx_t, exact=True), h.B, h.N) if need[1] else None
+        return (None, dx, *grads)

@@ -1299,3 +1299,128 @@ class PointTransformerLayer(nn.Module):
         p0, p2, a0, a2 = self.pos_mlp[0], self.pos_mlp[2], self.attn_mlp[0], self.attn_mlp[2]
         return pair_attn.point_transformer(x, pos, self.to_qkv.weight, p0.weight, p0.bias, p2.weight, p2.bias, a0.weight, a0.bias,
                                            a2.weight, a2.bias)
+
+
+# ----------------------------------------------------------------------------- the dense family of Common/utilities.py
+DENSE_K_MIN, DENSE_K_MAX = 2, 32       # the point itself + ops.knn(k - 1); spgan_knn selects at most 32
+
+
+def _dense_k(name: str, k) -> int:
+    if not isinstance(k, int) or not DENSE_K_MIN <= k <= DENSE_K_MAX:
+        raise ValueError("%s: k must be an integer in %d..%d (the point itself plus at most %d neighbours of the kNN kernel), got %r"
+                         % (name, DENSE_K_MIN, DENSE_K_MAX, DENSE_K_MAX - 1, k))
+    return k
+
+
+def get_graph_feature(x, k=20, idx=None):
+    """Common/ops.py:138-162: x [B,C,N] -> [B,2C,N,k] = cat[x_j - x_i, x_i] (the difference FIRST: the other way round from
+    get_edge_features) over the reference's own graph, the topk of the negative squared distance, in which every point is its own first
+    neighbour: rank 0 is the point itself, ranks 1..k-1 its nearest neighbours by ascending distance (ops.knn with k - 1).  idx: int64
+    local indices [B,N,k] (or [B,N*k]) as the reference's knn returns them, used instead.  k in 2..32.  The materialising function, for
+    parity; DenseEdgeModule never forms this tensor.  Differentiable in x through get_edge_features' backward."""
+    _require_gpu(x, "get_graph_feature")
+    k = _dense_k("get_graph_feature", k)
+    B, C, N = x.shape
+    x = x.contiguous()
+    if idx is None:
+        with torch.no_grad():
+            gidx = edge_conv.dense_graph(ops.cm_to_pm(x.detach()), B, N, k, 1 if C <= 4 else 0)
+            idx = ops.idx_to_local64(gidx, B, N)
+    else:
+        _require_gpu(idx, "get_graph_feature idx")
+        if idx.dtype != torch.int64 or idx.numel() != B * N * k:
+            raise ValueError("get_graph_feature: idx must be int64 with B*N*k = %d local indices, got %s %s" % (B * N * k, idx.dtype, tuple(idx.shape)))
+        if not ops.capturing() and (int(idx.min()) < 0 or int(idx.max()) >= N):
+            raise IndexError("get_graph_feature: a neighbour index lies outside [0, %d)" % N)
+    ee = get_edge_features(x, k, idx=idx.reshape(B, N * k))                   # cat[x_i, x_j - x_i]
+    return torch.cat([ee[:, C:], ee[:, :C]], dim=1)
+
+
+class DenseEdgeModule(nn.Module):
+    """Common/utilities.py:123-144: the densely connected EdgeConv, forward(x [B,C,N], idx=None) -> [B,growth_rate,N] = the max over the k
+    neighbours of the last of `levels` Conv2d 1x1 + BatchNorm2d + LeakyReLU(0.2) layers, each fed the concatenation of the edge
+    features cat[x_j - x_i, x_i] and every earlier level's output.  input_channel is the edge-feature width: 2*C.  Evaluated by
+    edge_conv.DenseEdgeFn: neither the [B,2C,N,k] edge tensor, nor a concatenation, nor an activated per-edge tensor exists in forward or
+    backward (per-edge storage: the pre-norm buffer [E, levels*growth_rate], in backward a gradient buffer of that size and one [E,
+    growth_rate] buffer).  Sub-modules carry the reference's names (dense_modules.{l}.{0,1,2}): state_dicts load strictly both ways.
+    The graph is the reference's (get_graph_feature: the point itself is a neighbour); k in 2..32.  idx (an extension): the graph to use
+    instead, int64 local indices [B,N,k] or [B,N*k] as the reference's knn returns them (range-checked), or int32 [B*N,k] global rows
+    (trusted).  last_idx: the graph of the latest forward.  Train and eval mode; once differentiable; exact fp32 products."""
+
+    def __init__(self, input_channel=64, levels=4, growth_rate=64, k=20):
+        super().__init__()
+        self.k = _dense_k("DenseEdgeModule", k)
+        if levels < 1 or growth_rate < 1 or input_channel < 2 or input_channel % 2:
+            raise ValueError("DenseEdgeModule: levels >= 1, growth_rate >= 1 and an even input_channel = 2*C are required, got (%r, %r, %r)"
+                             % (input_channel, levels, growth_rate))
+        self.input_channel = input_channel
+        self.dense_modules = nn.ModuleList()
+        c = input_channel
+        for _ in range(levels):
+            self.dense_modules.append(nn.Sequential(nn.Conv2d(c, growth_rate, kernel_size=1, bias=True), nn.BatchNorm2d(growth_rate),
+                                                    nn.LeakyReLU(negative_slope=0.2)))
+            c += growth_rate
+        self.last_idx: Optional[torch.Tensor] = None
+
+    def forward(self, x, idx: Optional[torch.Tensor] = None):
+        _require_gpu(x, "DenseEdgeModule")
+        if x.dim() != 3 or 2 * x.shape[1] != self.input_channel:
+            raise ValueError("DenseEdgeModule(input_channel=%d): x must be [B,%d,N] (input_channel = 2*C), got %s"
+                             % (self.input_channel, self.input_channel // 2, tuple(x.shape)))
+        bns = [m[1] for m in self.dense_modules]
+        G = self.dense_modules[0][0].out_channels
+        B, N, idx, knn_mode = check_edge_input("DenseEdgeModule", x, idx, self.k, x.shape[1], G, bns)
+        if idx is None and N < self.k:
+            raise ValueError("DenseEdgeModule: k=%d neighbours (the point itself included) need N >= %d points, got %d" % (self.k, self.k, N))
+        h = _Holder(B=B, N=N, k=self.k, training=self.training, idx=idx, knn_mode=knn_mode, bns=bns, last_idx=None)
+        params = [p for m in self.dense_modules for p in (m[0].weight, m[0].bias, m[1].weight, m[1].bias)]
+        out = edge_conv.DenseEdgeFn.apply(h, x.contiguous(), *params)
+        self.last_idx = h.last_idx
+        return out
+
+
+class DenseModule1D(nn.Module):
+    """Common/utilities.py:22-42: the per-point analogue, forward(x [B,in_dim,N]) -> [B,in_dim,N] = the last of `levels` Conv1d +
+    BatchNorm1d + LeakyReLU(0.2) layers, each fed the concatenation of x and every earlier level's output; the last level is in_dim wide.
+    Evaluated by edge_conv.DenseRowsFn without the concatenations.  Sub-modules as in the reference: state_dicts load strictly both ways."""
+
+    def __init__(self, in_dim=64, levels=3, growth_rate=64):
+        super().__init__()
+        if levels < 1 or growth_rate < 1 or in_dim < 1:
+            raise ValueError("DenseModule1D: in_dim, levels and growth_rate must be positive, got (%r, %r, %r)" % (in_dim, levels, growth_rate))
+        self.dense_modules = nn.ModuleList()
+        self.in_dim = in_dim
+        self.input_channel = in_dim
+        for i in range(levels):
+            if i == levels - 1:
+                growth_rate = in_dim
+            self.dense_modules.append(nn.Sequential(nn.Conv1d(self.input_channel, growth_rate, kernel_size=1, bias=True), nn.BatchNorm1d(growth_rate),
+                                                    nn.LeakyReLU(negative_slope=0.2)))
+            self.input_channel = self.input_channel + growth_rate
+
+    def forward(self, x):
+        _require_gpu(x, "DenseModule1D")
+        if x.dim() != 3 or x.shape[1] != self.in_dim:
+            raise ValueError("DenseModule1D(in_dim=%d): x must be [B,%d,N], got %s" % (self.in_dim, self.in_dim, tuple(x.shape)))
+        bns = [m[1] for m in self.dense_modules]
+        for bn in bns:
+            if bn.momentum is None or not bn.track_running_stats:
+                raise NotImplementedError("DenseModule1D: BatchNorm1d with momentum=None or track_running_stats=False is not supported")
+        h = _Holder(B=x.shape[0], N=x.shape[2], training=self.training, bns=bns)
+        params = [p for m in self.dense_modules for p in (m[0].weight, m[0].bias, m[1].weight, m[1].bias)]
+        return edge_conv.DenseRowsFn.apply(h, x.contiguous(), *params)
+
+
+class Dense_Attn(nn.Module):
+    """Common/utilities.py:292-321: forward(x [B,in_dim,N], res=True) -> dense(atten(x)) (+ x with res): Self_Attn followed by
+    DenseModule1D(in_dim, 3, in_dim).  `activation` is accepted and ignored, as in the reference."""
+
+    def __init__(self, in_dim=128, activation="relu"):
+        super().__init__()
+        self.atten = Self_Attn(in_dim=in_dim)
+        self.dense = DenseModule1D(in_dim=in_dim, levels=3, growth_rate=in_dim)
+
+    def forward(self, x, res=True):
+        pt = x
+        x = self.dense(self.atten(x))
+        return pt + x if res else x
