@@ -1201,6 +1201,48 @@ int spgan_edge_dense_scatter(const float* D, int ldd, const int32_t* rowptr, con
 int spgan_edge_dense_bn_apply(const float* g, int ldg, const float* z, int ldz, int M, int C, const float* mean, const float* invstd,
                               const float* gamma, const float* sums, int count, float* dz, int ldd, spgan_stream_t s);
 
+/* ------------------------------------------------------------------------------------------
+ * Global-context attention (csrc/gc_attn.hip): GC_attn of Common/utilities.py:357-426.  Per sample b over its L positions:
+ *   m_n = w . x_n + bias,  p = softmax_n(m)  (w == NULL: p_n = 1/L),  ctx = sum_n p_n x_n,
+ *   add = branch_add(ctx),  mul = sigmoid(branch_mul(ctx)),  branch = Conv1d(C,O,1) -> LayerNorm([O,1]) -> ReLU -> Conv1d(O,C,1),
+ *   out_n = x_n * mul + add.
+ * layout 0: channel-major, x / g / out / dx contiguous [B,C,L] (the ld arguments are not read).  layout 1: point-major rows [B*L, C] with
+ * row strides ld >= C.  16-byte accesses when L % 4 == 0 (layout 0) or C % 4 == 0 and every stride % 4 == 0 (layout 1) and the bases are
+ * 16-byte aligned; element accesses otherwise.  1 <= C, O <= 1024, 1 <= B <= 65535, L >= 1.  A workgroup reduces
+ * spgan_gc_attn_chunk_points(layout) positions of a sample; nch = ceil(L / that).  Every sum has a fixed order; no float atomics.
+ * Traffic: pool_fwd |x|, apply_fwd 2|x|, bwd_reduce 2|x|, bwd_apply 3|x|; layout 0 with C > 484 loads x twice in pool_fwd and bwd_apply
+ * (2|x| and 4|x|): the [C, 32] tile of the one-read kernels no longer fits 64 KB of LDS.
+ *   pool_fwd     part: workspace [B*nch*(C + 2)];  m [B*L]: the logits (not written when w == NULL);  ctx [B,C];  lse [B];
+ *                stat [B,2] = (max_n m_n, sum_n exp(m_n - max)), the form the backward evaluates p from.  Two launches.
+ *   channel_fwd  one launch for both branches (a NULL branch is skipped, its output untouched): hid [2,B,O] = the first convolution's
+ *                output, lnstat [2,B,2] = the LayerNorm's (mean, rstd), add / mul [B,C].  Branch 0 = add, 1 = mul.
+ *   channel_bwd  one launch: from dadd / dmul [B,C] (the cotangents of add / mul) -> dctx [B,C] and, per sample, the factors of the
+ *                parameter gradients G [B, nb*(C + 4*O)], nb = the number of branches, the add branch first, per branch
+ *                [dt (C) | dh (O) | dhn * xhat (O) | dhn (O) | r (O)]: dW2 = dt^T r, db2 = colsum dt, dW1 = dh^T ctx, db1 = colsum dh,
+ *                dLN.weight = colsum dhn * xhat, dLN.bias = colsum dhn.
+ *   apply_fwd    out = x * mul[b] + add[b] (NULL: 1 / 0).
+ *   bwd_reduce   dmul [B,C] = sum_n g_n * x_n, dadd [B,C] = sum_n g_n (either may be NULL); part: workspace [B*nch*2*C], layout 1 only.
+ *   bwd_apply    dx_n = g_n * mul + p_n dctx + s_n w,  s_n = p_n (dctx . x_n - dctx . ctx);  dwpart [B*nch, C]: per workgroup sum_n s_n x_n,
+ *                whose column sums are the gradient of w.  w == NULL: dx_n = g_n * mul + dctx / L; ctx, m, stat, dwpart are not read.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct spgan_gc_branch {
+  const float *W1, *b1, *lnw, *lnb, *W2, *b2; /* [O,C], [O], [O], [O], [C,O], [C] */
+} spgan_gc_branch_t;
+int spgan_gc_attn_chunk_points(int layout);
+int spgan_gc_attn_pool_fwd(const float* x, int layout, long ld, int B, int C, long L, const float* w, const float* bias, float* part, float* m,
+                           float* ctx, float* lse, float* stat, spgan_stream_t s);
+int spgan_gc_attn_channel_fwd(const float* ctx, int B, int C, int O, const spgan_gc_branch_t* add_p, const spgan_gc_branch_t* mul_p, float eps,
+                              float* hid, float* lnstat, float* add, float* mul, spgan_stream_t s);
+int spgan_gc_attn_channel_bwd(const float* dadd, const float* dmul, const float* mul, const float* hid, const float* lnstat, int B, int C, int O,
+                              const spgan_gc_branch_t* add_p, const spgan_gc_branch_t* mul_p, float* G, float* dctx, spgan_stream_t s);
+int spgan_gc_attn_apply_fwd(const float* x, int layout, long ldx, int B, int C, long L, const float* mul, const float* add, float* out, long ldo,
+                            spgan_stream_t s);
+int spgan_gc_attn_bwd_reduce(const float* x, long ldx, const float* g, long ldg, int layout, int B, int C, long L, float* part, float* dmul,
+                             float* dadd, spgan_stream_t s);
+int spgan_gc_attn_bwd_apply(const float* x, long ldx, const float* g, long ldg, int layout, int B, int C, long L, const float* mul,
+                            const float* dctx, const float* ctx, const float* w, const float* m, const float* stat, float* dx, long lddx,
+                            float* dwpart, spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

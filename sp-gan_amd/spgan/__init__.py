@@ -6,7 +6,7 @@
 Importing the package does not touch the GPU; the shared library is loaded on first use and its
 absence is a hard error (there is no CPU fallback).
 """
-from . import block_tail, dataset, edge_conv, edge_max, edge_rank, edge_weight, edge_window, fixture_rng, metrics, ops, pointconv_util, pointnet_util, point_attn, sampling  # noqa: F401
+from . import block_tail, dataset, edge_conv, edge_max, edge_rank, edge_weight, edge_window, fixture_rng, metrics, ops, pointconv_util, pointnet_util, point_attn, gc_attn, sampling  # noqa: F401
 from .capture import CapturedBody                                          # noqa: F401
 from .losses import GradientPenalty, dis_loss, gen_loss                    # noqa: F401
 from .modules import (AdaptivePointNorm, Discriminator, EdgeBlock, Generator, bilateral_upsample_edgeConv, conv2dbr, deform_edgeConv,   # noqa: F401
@@ -15,6 +15,7 @@ from .modules import (bilateral_block, bilateral_block_l1, bilateral_block_l2, b
                       deform_block_feat_middle, deform_block_middle, deform_block_tail)
 from .modules import Attention, PointTransformerLayer, Self_Attn            # noqa: F401
 from .modules import Dense_Attn, DenseEdgeModule, DenseModule1D, get_graph_feature            # noqa: F401
+from .modules import Dense_Attn_2D, DenseModule2D, GC_attn, MultiDenseMLP, Self_Attn2                                        # noqa: F401
 from .optim import EMA, Adam, StepLR, flatten_module                       # noqa: F401
 from .parallel import DataParallel, init_process_group_from_env, shard_batch   # noqa: F401
 from .train import TrainStep, requires_grad                                # noqa: F401
@@ -22,5 +23,5 @@ from .train import TrainStep, requires_grad                                # noq
 __all__ = ["Generator", "Discriminator", "EdgeBlock", "AdaptivePointNorm", "get_edge_features", "edgeConv", "conv2dbr", "upsample_edgeConv", "get_edge_features_xyz", "deform_edgeConv_simple",
            "deform_edgeConv_first", "deform_edgeConv_feat", "deform_edgeConv", "bilateral_upsample_edgeConv", "bilateral_block", "bilateral_block_l1",
            "bilateral_block_l2", "bilateral_block_l3", "bilateral_block_l4", "deform_block_middle", "deform_block_tail", "deform_block_feat_middle",
-           "deform_block_feat", "PointTransformerLayer", "Attention", "Self_Attn", "DenseEdgeModule", "DenseModule1D", "Dense_Attn", "get_graph_feature", "dis_loss", "gen_loss",
+           "deform_block_feat", "PointTransformerLayer", "Attention", "Self_Attn", "Self_Attn2", "DenseEdgeModule", "DenseModule1D", "Dense_Attn", "GC_attn", "DenseModule2D", "MultiDenseMLP", "Dense_Attn_2D", "get_graph_feature", "dis_loss", "gen_loss",
            "GradientPenalty", "TrainStep", "CapturedBody", "Adam", "EMA", "StepLR", "DataParallel", "requires_grad", "ops", "fixture_rng", "sampling"]

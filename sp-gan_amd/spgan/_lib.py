@@ -163,7 +163,13 @@ class SplitKMultiArgs(C.Structure):
                 ("beta", C.c_float * MULTI_MAX), ("block_start", C.c_int * (MULTI_MAX + 1))]
 
 
+class GcBranch(C.Structure):
+    """spgan_gc_branch_t: one Conv1d -> LayerNorm -> ReLU -> Conv1d branch of GC_attn"""
+    _fields_ = [("W1", C.c_void_p), ("b1", C.c_void_p), ("lnw", C.c_void_p), ("lnb", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p)]
+
+
 I, F, P, SZ = C.c_int, C.c_float, C.c_void_p, C.c_size_t
+LG, GCB = C.c_long, C.POINTER(GcBranch)
 
 # name -> (restype, argtypes).  Must list every symbol include/spgan_hip.h declares
 # (tests/test_abi.py cross-checks this table against the header and the .so).
@@ -382,6 +388,13 @@ SIGNATURES = {
     "spgan_edge_dense_level": (I, [P, I, I, P, P, F, P, I, P, P, I, I, P, I, I, I, I, P, I, P, P]),
     "spgan_edge_dense_scatter": (I, [P, I, P, P, I, I, I, P, I, P]),
     "spgan_edge_dense_bn_apply": (I, [P, I, P, I, I, I, P, P, P, P, I, P, I, P]),
+    "spgan_gc_attn_chunk_points": (I, [I]),
+    "spgan_gc_attn_pool_fwd": (I, [P, I, LG, I, I, LG, P, P, P, P, P, P, P, P]),
+    "spgan_gc_attn_channel_fwd": (I, [P, I, I, I, GCB, GCB, F, P, P, P, P, P]),
+    "spgan_gc_attn_channel_bwd": (I, [P, P, P, P, P, I, I, I, GCB, GCB, P, P, P]),
+    "spgan_gc_attn_apply_fwd": (I, [P, I, LG, I, I, LG, P, P, P, LG, P]),
+    "spgan_gc_attn_bwd_reduce": (I, [P, LG, P, LG, I, I, I, LG, P, P, P, P]),
+    "spgan_gc_attn_bwd_apply": (I, [P, LG, P, LG, I, I, I, LG, P, P, P, P, P, P, P, LG, P, P]),
 }
 
 _lib = None

@@ -33,7 +33,7 @@ Tensor = torch.Tensor
 
 # ----------------------------------------------------------------------------- operand images
 # one dictionary per builder: a layer that reaches the cap does not evict another layer's images
-_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}, "coord": {}, "bilateral": {}, "tail": {}, "dense_edge": {}, "dense_rows": {}}
+_IMAGES: Dict[str, Dict[tuple, tuple]] = {"upsample": {}, "rank": {}, "weight": {}, "coord": {}, "bilateral": {}, "tail": {}, "dense_edge": {}, "dense_rows": {}, "dense_side": {}}
 
 
 def cached_images(cache: Dict[tuple, tuple], weights: Sequence[Tensor], extra: tuple, build: Callable):
@@ -222,16 +222,18 @@ def dense_rows_images(Ws: Sequence[Tensor], Cin: int):
     """The operand images of DenseModule1D's conv weights (W_l [w_l, Cin + off_l, 1] over cat[x, y_1 .. y_{l-1}], off_l = w_1 + .. + w_{l-1}):
     (Wm = the weights as matrices; Wx_t [Cin, S] = the transposed x columns of every level side by side, S = sum w_l; Wback = per level
     m < L the stack [w_m, S - off_{m+1}] of the transposed y_m columns of every later level).  Cached per weight set (cached_images)."""
-    def build(*Ws):
-        L = len(Ws)
-        Wm = [W.reshape(W.shape[0], W.shape[1]).contiguous() for W in Ws]
-        off = [0]
-        for w in Wm:
-            off.append(off[-1] + w.shape[0])
-        Wx_t = torch.cat([w[:, :Cin].t() for w in Wm], dim=1).contiguous()
-        Wback = tuple(torch.cat([Wm[l][:, Cin + off[m]:Cin + off[m + 1]].t() for l in range(m + 1, L)], dim=1).contiguous() for m in range(L - 1))
-        return tuple(Wm), Wx_t, Wback
-    return cached_images(_IMAGES["dense_rows"], tuple(Ws), (Cin,), build)
+    return cached_images(_IMAGES["dense_rows"], tuple(Ws), (Cin,), lambda *Ws: _rows_images(Ws, Cin))
+
+
+def _rows_images(Ws: Sequence[Tensor], Cin: int):
+    L = len(Ws)
+    Wm = [W.reshape(W.shape[0], W.shape[1]).contiguous() for W in Ws]
+    off = [0]
+    for w in Wm:
+        off.append(off[-1] + w.shape[0])
+    Wx_t = torch.cat([w[:, :Cin].t() for w in Wm], dim=1).contiguous()
+    Wback = tuple(torch.cat([Wm[l][:, Cin + off[m]:Cin + off[m + 1]].t() for l in range(m + 1, L)], dim=1).contiguous() for m in range(L - 1))
+    return tuple(Wm), Wx_t, Wback
 
 
 # ----------------------------------------------------------------------------- what the Functions share
@@ -1163,65 +1165,119 @@ def dense_graph(x_pm: Tensor, B: int, N: int, k: int, knn_mode: int) -> Tensor:
     return idx
 
 
+def dense_side_images(Ws: Sequence[Tensor], widths: Sequence[int]):
+    """MultiDenseMLP's conv weights (W_l [w_l, K_l, 1, 1] over cat[x_0, y_0, x_1, y_1, .. y_{l-1}, x_l], Common/utilities.py:112-121) as
+    images over the buffer [x_0 .. x_{n-1} | z_0 .. z_{n-1}] DenseRowsFn keeps: level l's image [w_l, Cin + off_l] has its columns moved
+    to the buffer's order and ZERO columns for the side inputs x_j, j > l, it does not see yet (Cin = sum widths).
+    -> ((Wm, Wx_t, Wback) of the images as dense_rows_images forms them, maps): maps[l] int64 [K_l] = the buffer column of every column
+    of W_l.  One cache entry per weight set, in a dictionary of its own: the images are temporaries and never enter another cache."""
+    def build(*Ws):
+        n, Cin = len(Ws), sum(widths)
+        xoff, zoff = [0], [0]
+        for c in widths:
+            xoff.append(xoff[-1] + c)
+        for W in Ws:
+            zoff.append(zoff[-1] + W.shape[0])
+        maps, imgs = [], []
+        for l, W in enumerate(Ws):
+            spans = []
+            for j in range(l + 1):
+                spans.append((xoff[j], xoff[j + 1]))
+                if j < l:
+                    spans.append((Cin + zoff[j], Cin + zoff[j + 1]))
+            if sum(b - a for a, b in spans) != W.shape[1]:
+                raise ValueError("MultiDenseMLP: level %d's weight has %d input channels, the inputs give %d"
+                                 % (l, W.shape[1], sum(b - a for a, b in spans)))
+            m = torch.cat([torch.arange(a, b, dtype=torch.int64, device=W.device) for a, b in spans])   # built on the device: capturable
+            img = torch.zeros((W.shape[0], Cin + zoff[l]), dtype=torch.float32, device=W.device)
+            img[:, m] = W.reshape(W.shape[0], W.shape[1])
+            maps.append(m)
+            imgs.append(img)
+        return _rows_images(imgs, Cin), tuple(maps)
+    return cached_images(_IMAGES["dense_side"], tuple(Ws), tuple(widths), build)
+
+
 class DenseRowsFn(Function):
-    """out [B,Cin,N] = y_L, y_l = lrelu(bn_l(W_l . cat[x, y_1 .. y_{l-1}] + b_l), 0.2)   (the reference's DenseModule1D,
-    Common/utilities.py:22-42) without the concatenations or the activated tensors: one buffer R [M, Cin + S] = [x | z_1 | .. | z_L] of
+    """out [B,w_L,N] = y_L, y_l = lrelu(bn_l(W_l . cat[x, y_1 .. y_{l-1}] + b_l), slope)   (the reference's DenseModule1D / DenseModule2D,
+    Common/utilities.py:22-65) without the concatenations or the activated tensors: one buffer R [M, Cin + S] = [x | z_1 | .. | z_L] of
     the raw input and the pre-norm rows, each level a product over the columns in front of its slice with x taken as stored and the z
     columns activated while they are staged (csrc/edge_dense.hip, raw_cols = Cin).  The backward mirrors DenseEdgeFn's with k = 1.
-    holder: B, N, training, bns; parameters (W, b, gamma, beta) per level."""
+    holder: B, N, training, bns; parameters (W, b, gamma, beta) per level; the level widths are the weights'.  Optional holder fields:
+    slope (0.2; 0.0 = ReLU), name (the layer named in refusals), pm (x and out are point-major rows [M,C], no layout conversion) and
+    sides = the widths (c_0, .., c_{n-1}) of MultiDenseMLP's raw inputs: then x is followed by the n - 1 side inputs [B,c_i,N], the raw
+    block of R is [x_0 | .. | x_{n-1}] and the weights act through dense_side_images."""
 
     @staticmethod
-    def forward(ctx, h, x, *params):
+    def forward(ctx, h, x, *rest):
         from . import pointnet_util
-        B, Cin, N = x.shape
-        L, M, train = len(h.bns), B * N, h.training
+        slope, pm, sides = getattr(h, "slope", DENSE_SLOPE), getattr(h, "pm", False), getattr(h, "sides", None)
+        ns = len(sides) - 1 if sides else 0
+        xs, params = (x,) + tuple(rest[:ns]), rest[ns:]
+        L, M, train = len(h.bns), h.B * h.N, h.training
         Ws, bs, gammas, betas = params[0::4], params[1::4], params[2::4], params[3::4]
-        Wm, _, _ = dense_rows_images(Ws, Cin)
+        Cin = sum(sides) if sides else x.shape[1]
+        maps = None
+        if sides:
+            (Wm, _, _), maps = dense_side_images(Ws, sides)
+        else:
+            Wm, _, _ = dense_rows_images(Ws, Cin)
         off = [Cin]
         for w in Wm:
             off.append(off[-1] + w.shape[0])
         R = torch.empty((M, off[-1]), dtype=torch.float32, device=x.device)
-        pointnet_util._cm_to_rows(x.contiguous(), R, 0)
+        if pm:
+            R[:, :Cin].copy_(x)
+        else:
+            col = 0
+            for t in xs:
+                pointnet_util._cm_to_rows(t.contiguous(), R, col)
+                col += t.shape[1]
         SC = torch.empty((2, off[-1]), dtype=torch.float32, device=x.device)  # (scale | shift) per column of R; the x columns are not read
         sts = []
         for l in range(L):
             lo, hi = off[l], off[l + 1]
-            res = edge_dense.edge_dense_level(R[:, :lo], Wm[l], R[:, lo:hi], raw_cols=Cin, scale=SC[0, :lo], shift=SC[1, :lo], slope=DENSE_SLOPE,
+            res = edge_dense.edge_dense_level(R[:, :lo], Wm[l], R[:, lo:hi], raw_cols=Cin, scale=SC[0, :lo], shift=SC[1, :lo], slope=slope,
                                               bias=bs[l].detach(), stats=train)
             st = bn_stats(h.bns[l], train, M, gammas[l], betas[l], records=res[1:] if train else None)
             SC[:, lo:hi] = st[:2]
             sts.append(st)
-        out_pm = ops.affine_act(R[:, off[-2]:], sts[-1][0], sts[-1][1], DENSE_SLOPE)
-        ctx.h, ctx.sts, ctx.off = h, sts, off
+        out_pm = ops.affine_act(R[:, off[-2]:], sts[-1][0], sts[-1][1], slope)
+        ctx.h, ctx.sts, ctx.off, ctx.ns = h, sts, off, ns
         ctx.save_for_backward(R, out_pm, SC, *Ws, *gammas)
-        return ops.pm_to_cm(out_pm, B, N)
+        return out_pm if pm else ops.pm_to_cm(out_pm, h.B, h.N)
 
     @staticmethod
     def backward(ctx, dout):
-        refuse_double_backward("DenseModule1D")
+        refuse_double_backward(getattr(ctx.h, "name", "DenseModule1D"))
         return DenseRowsFn._backward(ctx, dout)
 
     @staticmethod
     @once_differentiable
     def _backward(ctx, dout):
         from . import pointnet_util
-        h, sts, off = ctx.h, ctx.sts, ctx.off
+        h, sts, off, ns = ctx.h, ctx.sts, ctx.off, ctx.ns
+        slope, pm, sides = getattr(h, "slope", DENSE_SLOPE), getattr(h, "pm", False), getattr(h, "sides", None)
         L = len(sts)
         R, out_pm, SC = ctx.saved_tensors[:3]
         Ws, gammas = ctx.saved_tensors[3:3 + L], ctx.saved_tensors[3 + L:]
         M, Cin, train = R.shape[0], off[0], h.training
         need = ctx.needs_input_grad
-        _, Wx_t, Wback = dense_rows_images(Ws, Cin)
+        p0 = 2 + ns                                                                    # the first parameter's position among the inputs
+        maps = None
+        if sides:
+            (_, Wx_t, Wback), maps = dense_side_images(Ws, sides)
+        else:
+            _, Wx_t, Wback = dense_rows_images(Ws, Cin)
         D = torch.empty((M, off[-1] - Cin), dtype=torch.float32, device=R.device)      # column c of D belongs to column Cin + c of R
         sums = [None] * L
         _, _, inv, mu = sts[-1]
-        r, sums[-1] = pointnet_util._group_max_bwd(ops.cm_to_pm(dout), out_pm, None, R[:, off[-2]:], mu, inv, DENSE_SLOPE, 1)
+        r, sums[-1] = pointnet_util._group_max_bwd(dout.contiguous() if pm else ops.cm_to_pm(dout), out_pm, None, R[:, off[-2]:], mu, inv, slope, 1)
         edge_dense.edge_dense_bn_apply(r, R[:, off[-2]:], mu, inv, gammas[-1], used(sums[-1], train), M, D[:, off[-2] - Cin:])
         del r
         for m in range(L - 2, -1, -1):
             lo, hi = off[m], off[m + 1]
             sc, sh, inv, mu = sts[m]
-            gz, t1, t2 = ops.gemm_nt_bnbwd(D[:, hi - Cin:], Wback[m], R[:, lo:hi], sc, sh, mu, inv, DENSE_SLOPE, exact=True)
+            gz, t1, t2 = ops.gemm_nt_bnbwd(D[:, hi - Cin:], Wback[m], R[:, lo:hi], sc, sh, mu, inv, slope, exact=True)
             sums[m] = torch.cat([t1, t2])
             edge_dense.edge_dense_bn_apply(gz, R[:, lo:hi], mu, inv, gammas[m], used(sums[m], train), M, D[:, lo - Cin:hi - Cin])
             del gz
@@ -1230,12 +1286,25 @@ class DenseRowsFn(Function):
             lo, hi = off[l], off[l + 1]
             Dl = D[:, lo - Cin:hi - Cin]
             dW = None
-            if need[2 + 4 * l]:
+            if need[p0 + 4 * l]:
                 parts = [ops.gemm_tn(Dl, R[:, :Cin], exact=True)]
                 if l:
-                    parts.append(ops.gemm_tn(Dl, R[:, Cin:lo], pro=(SC[0, Cin:lo], SC[1, Cin:lo], DENSE_SLOPE), exact=True))
-                dW = torch.cat(parts, dim=1).view_as(Ws[l])
-            db = dbias(Dl, train) if need[3 + 4 * l] else None
-            grads += [dW, db, *gb(sums[l], need, 4 + 4 * l)]
-        dx = ops.pm_to_cm(ops.gemm_nt(D, Wx_t, exact=True), h.B, h.N) if need[1] else None
-        return (None, dx, *grads)
+                    parts.append(ops.gemm_tn(Dl, R[:, Cin:lo], pro=(SC[0, Cin:lo], SC[1, Cin:lo], slope), exact=True))
+                dW = torch.cat(parts, dim=1)
+                dW = (dW if maps is None else dW[:, maps[l]]).reshape(Ws[l].shape)
+            db = dbias(Dl, train) if need[p0 + 1 + 4 * l] else None
+            grads += [dW, db, *gb(sums[l], need, p0 + 2 + 4 * l)]
+        dxs = [None] * (1 + ns)
+        if any(need[1:p0]):
+            dR = ops.gemm_nt(D, Wx_t, exact=True)
+            if pm:
+                dxs[0] = dR
+            elif not sides:
+                dxs[0] = ops.pm_to_cm(dR, h.B, h.N)
+            else:
+                col = 0
+                for i, c in enumerate(sides):
+                    if need[1 + i]:
+                        dxs[i] = pointnet_util._rows_to_cm(dR, col, h.B, c, h.N)
+                    col += c
+        return (None, *dxs, *grads)

@@ -1424,3 +1424,238 @@ class Dense_Attn(nn.Module):
         pt = x
         x = self.dense(self.atten(x))
         return pt + x if res else x
+
+
+class GC_attn(nn.Module):
+    """Common/utilities.py:357-426: global-context attention, forward(x [B,in_dim,...]) -> x * mul + add of the input's shape, with
+    ctx = sum_n softmax_n(conv_mask(x))_n x_n (pool='att') or the mean over the positions (a pool string without 'att'), and
+    add = channel_add_conv(ctx), mul = channel_mul_conv(ctx) (Conv1d -> LayerNorm -> ReLU -> Conv1d [-> Sigmoid]); the multiplication
+    comes first, a fusion that is not listed is skipped, no fusion at all returns x.  The children are parameter containers created in
+    the reference's order (state_dicts load strictly both ways, a seed gives the reference's initial values); forward runs spgan.gc_attn:
+    two reads of x per direction, cost linear in the number of positions, nothing of x's size saved but x.  1 <= in_dim, out_dim <= 1024.
+    A pool string that contains 'att' without being 'att' builds a module the reference cannot run: ValueError here.  Once differentiable."""
+
+    def __init__(self, in_dim, out_dim=None, pool="att", fusions=["channel_add", "channel_mul"]):
+        super().__init__()
+        from . import gc_attn
+        self.in_dim = int(in_dim)
+        self.out_dim = int(out_dim) if out_dim is not None else self.in_dim
+        if not isinstance(pool, str) or ("att" in pool and pool != "att"):
+            raise ValueError("GC_attn: pool must be 'att' or a string without 'att' (average pooling), got %r" % (pool,))
+        gc_attn.check_dims(1, self.in_dim, 1, self.out_dim)
+        self.pool = pool
+        self.fusions = fusions
+        if pool == "att":
+            self.conv_mask = nn.Conv1d(self.in_dim, 1, kernel_size=1)
+            self.softmax = nn.Softmax(dim=2)
+        else:
+            self.avg_pool = nn.AdaptiveAvgPool1d(1)
+
+        def branch(sigmoid):
+            layers = [nn.Conv1d(self.in_dim, self.out_dim, kernel_size=1), nn.LayerNorm([self.out_dim, 1]), nn.ReLU(inplace=True),
+                      nn.Conv1d(self.out_dim, self.in_dim, kernel_size=1)]
+            return nn.Sequential(*(layers + ([nn.Sigmoid()] if sigmoid else [])))
+        self.channel_add_conv = branch(False) if "channel_add" in fusions else None
+        self.channel_mul_conv = branch(True) if "channel_mul" in fusions else None
+
+    def _apply_fn(self, x, layout, B, L):
+        from . import gc_attn
+        add, mul = self.channel_add_conv, self.channel_mul_conv
+        params = []
+        if self.pool == "att":
+            params += [self.conv_mask.weight, self.conv_mask.bias]
+        eps = 1e-5
+        for br in (add, mul):
+            if br is not None:
+                if not br[1].elementwise_affine:
+                    raise NotImplementedError("GC_attn: a LayerNorm without elementwise_affine is not supported")
+                eps = float(br[1].eps)
+                params += [br[0].weight, br[0].bias, br[1].weight, br[1].bias, br[3].weight, br[3].bias]
+        h = _Holder(layout=layout, B=B, L=L, att=self.pool == "att", has_add=add is not None, has_mul=mul is not None, eps=eps)
+        return gc_attn.GCAttnFn.apply(h, x, *params)
+
+    def _check(self, x):
+        _require_gpu(x, "GC_attn")
+        if x.dtype != torch.float32:
+            raise TypeError("GC_attn: x must be float32, got %s" % x.dtype)
+
+    def forward_pm(self, x_pm, B: int, L: int):
+        """x_pm [B*L, in_dim] point-major rows (the row stride may exceed in_dim) -> [B*L, in_dim]"""
+        self._check(x_pm)
+        if x_pm.dim() != 2 or tuple(x_pm.shape) != (B * L, self.in_dim):
+            raise ValueError("GC_attn.forward_pm: x must be [%d,%d] rows, got %s" % (B * L, self.in_dim, tuple(x_pm.shape)))
+        if self.channel_add_conv is None and self.channel_mul_conv is None:
+            return x_pm
+        return self._apply_fn(x_pm, "pm", B, L)
+
+    def forward(self, x):
+        self._check(x)
+        if x.dim() < 3 or x.shape[1] != self.in_dim or x.numel() == 0:
+            raise ValueError("GC_attn(in_dim=%d): x must be a non-empty [B,%d,...] tensor with dim >= 3, got %s" % (self.in_dim, self.in_dim, tuple(x.shape)))
+        if self.channel_add_conv is None and self.channel_mul_conv is None:
+            return x
+        size = x.shape
+        flat = x.reshape(size[0], size[1], -1)
+        return self._apply_fn(flat, "cm", size[0], flat.shape[2]).view(*size)
+
+
+def _check_f32(t: torch.Tensor, what: str):
+    _require_gpu(t, what)
+    if t.dtype != torch.float32:
+        raise TypeError("%s: inputs must be float32, got %s" % (what, t.dtype))
+
+
+def _check_bns(what, bns):
+    for bn in bns:
+        if bn.momentum is None or not bn.track_running_stats:
+            raise NotImplementedError("%s: a BatchNorm with momentum=None or track_running_stats=False is not supported" % what)
+
+
+class DenseModule2D(nn.Module):
+    """Common/utilities.py:45-65: forward(x [B,in_dim,H,W]) -> [B,mlps[-1],H,W] = the last of len(mlps) - 1 Conv2d 1x1 + BatchNorm2d +
+    LeakyReLU(0.2) layers over the B*H*W positions, level i (mlps[i] wide, i >= 1) fed the concatenation of x and every earlier level's
+    output.  levels, growth_rate and mlps[0] are ignored, as in the reference; fewer than two entries of mlps leave the reference without
+    a layer (its forward fails): ValueError here.  Evaluated by edge_conv.DenseRowsFn without the concatenations.  Sub-modules as in the
+    reference: state_dicts load strictly both ways.  forward_pm(x [B*L, in_dim] rows, B, L) -> [B*L, mlps[-1]] rows."""
+
+    def __init__(self, in_dim=64, levels=3, growth_rate=64, mlps=[]):
+        super().__init__()
+        if len(mlps) < 2 or in_dim < 1 or any(int(w) < 1 for w in mlps[1:]):
+            raise ValueError("DenseModule2D: mlps must list at least two widths (mlps[0] is ignored) and every width must be positive, got in_dim=%r mlps=%r"
+                             % (in_dim, mlps))
+        self.dense_modules = nn.ModuleList()
+        self.in_dim = in_dim
+        self.input_channel = in_dim
+        for i in range(1, len(mlps)):
+            growth_rate = mlps[i]
+            self.dense_modules.append(nn.Sequential(nn.Conv2d(self.input_channel, growth_rate, kernel_size=1, bias=True), nn.BatchNorm2d(growth_rate),
+                                                    nn.LeakyReLU(negative_slope=0.2)))
+            self.input_channel = self.input_channel + growth_rate
+
+    def _run(self, x, B, L, pm):
+        bns = [m[1] for m in self.dense_modules]
+        _check_bns("DenseModule2D", bns)
+        h = _Holder(B=B, N=L, training=self.training, bns=bns, pm=pm, name="DenseModule2D")
+        params = [p for m in self.dense_modules for p in (m[0].weight, m[0].bias, m[1].weight, m[1].bias)]
+        return edge_conv.DenseRowsFn.apply(h, x, *params)
+
+    def forward_pm(self, x_pm, B: int, L: int):
+        _check_f32(x_pm, "DenseModule2D")
+        if x_pm.dim() != 2 or tuple(x_pm.shape) != (B * L, self.in_dim):
+            raise ValueError("DenseModule2D.forward_pm: x must be [%d,%d] rows, got %s" % (B * L, self.in_dim, tuple(x_pm.shape)))
+        return self._run(x_pm, B, L, True)
+
+    def forward(self, x):
+        _check_f32(x, "DenseModule2D")
+        if x.dim() != 4 or x.shape[1] != self.in_dim:
+            raise ValueError("DenseModule2D(in_dim=%d): x must be [B,%d,H,W], got %s" % (self.in_dim, self.in_dim, tuple(x.shape)))
+        B, _, H, W = x.shape
+        return self._run(x.reshape(B, self.in_dim, H * W).contiguous(), B, H * W, False).view(B, -1, H, W)
+
+
+class MultiDenseMLP(nn.Module):
+    """Common/utilities.py:92-121: forward(x: list, x[i] [B,mlps2[i],H,W]) -> [B,mlps[-1],H,W].  Level i is Conv2d 1x1 (-> mlps[i]) +
+    BatchNorm2d + ReLU over pc, and pc = cat[pc, y_i, x[i+1]] feeds the next one.  Evaluated by edge_conv.DenseRowsFn with slope 0 on one
+    buffer [x_0 .. x_{n-1} | z_0 ..]: a level's weight image has zero columns for the side inputs it does not see yet
+    (edge_conv.dense_side_images).  Gradients reach every x[i] and every parameter.  Sub-modules as in the reference."""
+
+    def __init__(self, mlps, mlps2):
+        super().__init__()
+        if len(mlps) != len(mlps2) or len(mlps) < 1 or any(int(w) < 1 for w in list(mlps) + list(mlps2)):
+            raise ValueError("MultiDenseMLP: mlps and mlps2 must be equally long lists of positive widths, got %r and %r" % (mlps, mlps2))
+        self.mlps, self.mlps2 = [int(w) for w in mlps], [int(w) for w in mlps2]
+        self.dense_modules = nn.ModuleList()
+        c_in = mlps2[0]
+        for i in range(len(mlps)):
+            c_out = mlps[i]
+            self.dense_modules.append(nn.Sequential(nn.Conv2d(c_in, c_out, kernel_size=1, bias=True), nn.BatchNorm2d(c_out), nn.ReLU(inplace=True)))
+            if i < len(mlps) - 1:
+                c_in = c_in + c_out + mlps2[i + 1]
+
+    def forward(self, x):
+        n = len(self.mlps)
+        if not isinstance(x, (list, tuple)) or len(x) != n:
+            raise ValueError("MultiDenseMLP: x must be a list of %d tensors, got %r" % (n, type(x)))
+        for i, t in enumerate(x):
+            _check_f32(t, "MultiDenseMLP")
+            if t.dim() != 4 or t.shape[1] != self.mlps2[i] or t.shape[0] != x[0].shape[0] or t.shape[2:] != x[0].shape[2:]:
+                raise ValueError("MultiDenseMLP: x[%d] must be [B,%d,H,W] like x[0], got %s" % (i, self.mlps2[i], tuple(t.shape)))
+        B, _, H, W = x[0].shape
+        bns = [m[1] for m in self.dense_modules]
+        _check_bns("MultiDenseMLP", bns)
+        h = _Holder(B=B, N=H * W, training=self.training, bns=bns, slope=0.0, sides=tuple(self.mlps2), name="MultiDenseMLP")
+        params = [p for m in self.dense_modules for p in (m[0].weight, m[0].bias, m[1].weight, m[1].bias)]
+        flat = [t.reshape(B, t.shape[1], H * W).contiguous() for t in x]
+        return edge_conv.DenseRowsFn.apply(h, *flat, *params).view(B, -1, H, W)
+
+
+class Dense_Attn_2D(nn.Module):
+    """Common/utilities.py:323-353: forward(x [B,in_dim,H,W], res=True) -> atten(dense(x)) [B,mlps[-1],H,W] with dense =
+    DenseModule2D(in_dim, mlps=mlps) and atten = GC_attn(mlps[-1]) (atten='gc') or Self_Attn(mlps[-1]) (anything else), created in the
+    reference's order (atten first).  res and activation are accepted and ignored, as in the reference.  The chain runs on point-major
+    rows over the L = H*W positions (dense.forward_pm, atten.forward_pm): one layout conversion at each end, and with Self_Attn no
+    [B,L,L] map."""
+
+    def __init__(self, in_dim=128, activation="relu", mlps=[], atten="gc"):
+        super().__init__()
+        if len(mlps) < 2:
+            raise ValueError("Dense_Attn_2D: mlps must list at least two widths, got %r" % (mlps,))
+        self.atten = GC_attn(in_dim=mlps[-1]) if atten == "gc" else Self_Attn(in_dim=mlps[-1])
+        self.dense = DenseModule2D(in_dim=in_dim, mlps=mlps)
+
+    def forward(self, x, res=True):
+        _check_f32(x, "Dense_Attn_2D")
+        if x.dim() != 4 or x.shape[1] != self.dense.in_dim:
+            raise ValueError("Dense_Attn_2D: x must be [B,%d,H,W], got %s" % (self.dense.in_dim, tuple(x.shape)))
+        B, C, H, W = x.shape
+        L = H * W
+        y = self.dense.forward_pm(Fn.CmToPm.apply(x.reshape(B, C, L)), B, L)
+        y = self.atten.forward_pm(y, B, L)
+        return Fn.PmToCm.apply(y, B, L).view(B, -1, H, W)
+
+
+class Self_Attn2(nn.Module):
+    """Common/utilities.py:247-290: Self_Attn whose query / key / value are Sequential(Conv1d, BatchNorm1d, LeakyReLU(0.2)).
+    forward(x [B,in_dim,...]) -> gamma * attn + x of x's shape, out[:, :, j] = sum_i softmax_i(query_i . key_j) value_i over the
+    flattened positions.  Runs on spgan.point_attn (no [B,N,N] map) with the existing GEMM, BatchNorm and activation launches; train
+    and eval mode; in_dim in 8..512 (ValueError otherwise) and B * N * in_dim a multiple of 4.  The state_dict (gamma first, 22
+    entries) loads strictly both ways.  `activation` is stored and unused, as in the reference.  Once differentiable."""
+
+    def __init__(self, in_dim: int = 128, activation: str = "relu"):
+        super().__init__()
+        from . import point_attn
+        in_dim = int(in_dim)
+        try:
+            point_attn.padded_dk(in_dim // 8)
+            point_attn.padded_dv(in_dim)
+        except ValueError as e:
+            raise ValueError("Self_Attn2(in_dim=%d): %s" % (in_dim, e)) from None
+        self.chanel_in = in_dim
+        self.activation = activation
+
+        def proj(out):
+            return nn.Sequential(nn.Conv1d(in_channels=in_dim, out_channels=out, kernel_size=1, bias=True), nn.BatchNorm1d(out),
+                                 nn.LeakyReLU(negative_slope=0.2))
+        self.query = proj(in_dim // 8)
+        self.key = proj(in_dim // 8)
+        self.value = proj(in_dim)
+        self.gamma = nn.Parameter(torch.zeros(1))
+
+    def forward_pm(self, x_pm, B: int, N: int):
+        from . import point_attn
+        _check_f32(x_pm, "Self_Attn2")
+        if x_pm.dim() != 2 or tuple(x_pm.shape) != (B * N, self.chanel_in):
+            raise ValueError("Self_Attn2.forward_pm: x must be [%d,%d] rows, got %s" % (B * N, self.chanel_in, tuple(x_pm.shape)))
+        bns = [self.query[1], self.key[1], self.value[1]]
+        _check_bns("Self_Attn2", bns)
+        params = [p for m in (self.query, self.key, self.value) for p in (m[0].weight, m[0].bias, m[1].weight, m[1].bias)]
+        return point_attn.SelfAttn2Fn.apply(_Holder(B=B, N=N, training=self.training, bns=bns), x_pm, *params, self.gamma)
+
+    def forward(self, x):
+        _check_f32(x, "Self_Attn2")
+        if x.dim() < 3 or x.shape[1] != self.chanel_in:
+            raise ValueError("Self_Attn2: x must be [B,%d,...], got %s" % (self.chanel_in, tuple(x.shape)))
+        size = x.shape
+        flat = x.reshape(size[0], size[1], -1)
+        N = flat.shape[2]
+        return Fn.PmToCm.apply(self.forward_pm(Fn.CmToPm.apply(flat), size[0], N), size[0], N).view(*size)

@@ -220,3 +220,86 @@ class SelfAttnFn(Function):
                  dW[lo["k"]:lo["k"] + dk].reshape(Wk.shape), db[lo["k"]:lo["k"] + dk].contiguous(),
                  dW[lo["v"]:lo["v"] + dv].reshape(Wv.shape), db[lo["v"]:lo["v"] + dv].contiguous(), dgamma.reshape(gamma.shape)]
         return (None, dx) + Fn._deliver((Wq, bq, Wk, bk, Wv, bv, gamma), grads, ctx.needs_input_grad[2:], ctx.fused)
+
+
+SA2_SLOPE = 0.2
+
+
+class SelfAttn2Fn(Function):
+    """spgan.Self_Attn2 (Common/utilities.py:247-290) on point-major rows: x [B*N,C], then (conv weight, conv bias, bn weight, bn bias) of
+    query, key and value and gamma.  Each projection is Conv1d -> BatchNorm1d -> LeakyReLU(0.2); the softmax runs over the first point
+    index as in Self_Attn, so the activated `key` is the core's q and the activated `query` its k.  One stacked product
+    [key | query | value] with its column statistics, one finalise per BatchNorm (running statistics advanced in the order query, key,
+    value), one activation pass, the core, the residual.  holder: B, N, training, bns = (query, key, value)'s BatchNorm1d."""
+
+    @staticmethod
+    def forward(ctx, holder, x, Wq, bq, gq, eq, Wk, bk, gk, ek, Wv, bv, gv, ev, gamma):
+        from . import functions as Fn
+        from .edge_conv import bn_stats
+        Fn._record_modes(ctx, holder)
+        h = holder
+        x = x.contiguous()
+        M = x.shape[0]
+        W, dims = stacked_weight(Wk, Wq, Wv)                    # core q <- key, core k <- query
+        dk, dkp, dv, dvp = dims
+        bias = stacked_bias(bk, bq, bv, dims)
+        if h.training:
+            cat, mean, var = ops.gemm_nt(x, W, bias, stats=True, exact=True)
+        else:
+            cat, mean, var = ops.gemm_nt(x, W, bias, exact=True), None, None
+        lo = {"k": 0, "q": dkp, "v": 2 * dkp}
+        width = {"k": dk, "q": dk, "v": dv}
+        ST = torch.zeros((4, W.shape[0]), dtype=torch.float32, device=x.device)       # (scale, shift, invstd, mean); padding columns stay 0
+        GA = torch.zeros((W.shape[0],), dtype=torch.float32, device=x.device)
+        for name, bn, g_, e_ in (("q", h.bns[0], gq, eq), ("k", h.bns[1], gk, ek), ("v", h.bns[2], gv, ev)):
+            a, b_ = lo[name], lo[name] + width[name]
+            mom = None if mean is None else (mean[a:b_].contiguous(), var[a:b_].contiguous())
+            ST[:, a:b_] = bn_stats(bn, h.training, M, g_.detach(), e_.detach(), moments=mom)
+            GA[a:b_] = g_.detach()
+        act = ops.affine_act(cat, ST[0], ST[1], SA2_SLOPE)
+        o, lse = point_attn_fwd(act[:, :dkp], act[:, dkp:2 * dkp], act[:, 2 * dkp:], h.B, h.N)
+        ov = o if o.shape[1] == dv else o[:, :dv].contiguous()
+        y = ops.scale_residual(ov, x, gamma)
+        ctx.save_for_backward(x, cat, act, ov, lse, W, ST, GA, gamma, Wq, bq, gq, eq, Wk, bk, gk, ek, Wv, bv, gv, ev)
+        ctx.dims, ctx.h = dims, h
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        refuse_double_backward("Self_Attn2")
+        return SelfAttn2Fn._backward(ctx, dy)
+
+    @staticmethod
+    @once_differentiable
+    def _backward(ctx, dy):
+        from . import edge_dense, pointnet_util
+        from . import functions as Fn
+        from .edge_conv import used
+        x, cat, act, ov, lse, W, ST, GA, gamma, *prm = ctx.saved_tensors
+        Wq, bq, gq, eq, Wk, bk, gk, ek, Wv, bv, gv, ev = prm
+        dk, dkp, dv, dvp = ctx.dims
+        h = ctx.h
+        M, Wt = cat.shape
+        dy = dy.contiguous()
+        d_o, dgamma = ops.scale_residual_bwd(dy, ov, gamma)
+        dact = projected_backward(act, lse, _pad_cols(d_o, dvp), ctx.dims, h.B, h.N)
+        # LeakyReLU and BatchNorm of all three projections at once: the mask from the activated value, the two column sums, then dz
+        r, sums = pointnet_util._group_max_bwd(dact, act, None, cat, ST[3], ST[2], SA2_SLOPE, 1)
+        dz = torch.empty_like(cat)
+        edge_dense.edge_dense_bn_apply(r, cat, ST[3], ST[2], GA, used(sums, h.training), M, dz)
+        del r, dact
+        dW = ops.gemm_tn(dz, x, exact=True)
+        db = None if h.training else ops.colsum(dz)[0]
+        dx = None
+        if ctx.needs_input_grad[1]:
+            dx = ops.gemm_nt(dz, W.t().contiguous(), exact=True)
+            ops.multi_add([dx], [dy])
+        lo = {"k": 0, "q": dkp, "v": 2 * dkp}
+        grads = []
+        for name, Wp, bp, f in (("q", Wq, bq, dk), ("k", Wk, bk, dk), ("v", Wv, bv, dv)):
+            a, b_ = lo[name], lo[name] + f
+            # a conv bias in front of a train-mode BatchNorm: the batch mean absorbs it, an exact zero
+            grads += [dW[a:b_].reshape(Wp.shape), 0 if db is None else db[a:b_].contiguous(), sums[Wt + a:Wt + b_].contiguous(),
+                      sums[a:b_].contiguous()]
+        grads.append(dgamma.reshape(gamma.shape))
+        return (None, dx) + Fn._deliver(tuple(prm) + (gamma,), grads, ctx.needs_input_grad[2:], ctx.fused)
