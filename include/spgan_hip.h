@@ -1243,6 +1243,46 @@ int spgan_gc_attn_bwd_apply(const float* x, long ldx, const float* g, long ldg, 
                             const float* dctx, const float* ctx, const float* w, const float* m, const float* stat, float* dx, long lddx,
                             float* dwpart, spgan_stream_t s);
 
+/* ------------------------------------------------------------------------------------------
+ * MST expansion penalty and minimum-density sampling (csrc/expansion.hip): metrics/expansion_penalty/expansion_penalty_cuda.cu
+ * and metrics/MDS/MDS_cuda.cu of the reference.  No float atomics, no adjacency workspace, every sum in a fixed order: results repeat bit for bit.
+ *
+ * spgan_expansion_penalty_fwd: xyz [B,n,3]; every run of primitive_size (p) consecutive points of a cloud is one primitive,
+ * 2 <= p <= 512, n % p == 0.  Per primitive:
+ *   1. Prim's algorithm from local point 0.  Edge length sqrtf((dx*dx + dy*dy) + dz*dz), each operation rounded on its own.  A candidate's
+ *      parent changes only on a strictly smaller distance; the next vertex is the unvisited one of least distance, the HIGHEST local index
+ *      among exact ties (the reference's reduction tree at power-of-two p; at other p that tree is not a minimum, this is the true arg-min).
+ *   2. mean = (sum of the p-1 edge lengths) / (float)(p-1) -> prim_mean_ws [B * n/p].  Order of the sum, with w[v] the length of the edge
+ *      that attached vertex v (w[0] = 0, w[v] = 0 for v >= p): s_l = (..((w[l] + w[64+l]) + w[128+l]) + ..) for l = 0..63, then for
+ *      o = 32, 16, 8, 4, 2, 1: s_l = s_l + s_(l xor o) on all l at once; the sum is s_0.  mean_mst_length[b] = the same two-stage sum over the
+ *      cloud's primitive means m[j] (s_l over j = l, l+64, ..), divided by (float)(n/p).
+ *   3. Leaf peeling in synchronous rounds assigns each tree edge to one endpoint: the leaves of a round are the vertices of remaining
+ *      degree 1 at its start; leaf t with remaining neighbour u takes the edge when cnt_start[u] > 1, or cnt_start[u] == 1 and t > u.
+ *      (One of the outcomes the reference's racing loop can produce: the one where every read precedes every decrement.)
+ *   4. An owned edge of length c > mean * alpha (a float product): dist[b, base+t] = c, assignment[b, base+t] = base_in_cloud + u;
+ *      every other point: dist 0, assignment -1.
+ * spgan_expansion_penalty_bwd: grad_xyz[b,j] = 2 * grad_dist[b,j] * (xyz[b,j] - xyz[b, assignment[b,j]]) where assignment != -1, else 0
+ *   (only the owning endpoint receives a gradient and the factor is that of a squared length: both as the reference); plain stores.
+ * spgan_minimum_density_sample: xyz [B,n,3] -> out int32 [B,npoint], 1 <= npoint <= n.  t = 5 * L * L (in double, rounded once), L =
+ *   mean_mst_length[b]; out[0] = 0; a density T[k] starts at 0 and is set to 1e9 once k is selected; for j = 1 .. npoint-1 every k adds
+ *   w_k * expf(-d_k / t), d_k = (dx*dx + dy*dy) + dz*dz to the last selected point, w_k = 1 for k < split else 2 (the reference hard-codes
+ *   8192), and the point of least T is selected, the LOWEST index among exact ties (the reference: by thread id, which depends on its
+ *   block size).  density_ws [B*n] is read only when spgan_minimum_density_sample_needs_ws(n) != 0 (n > 16384) and may be NULL otherwise.
+ * spgan_gather_points_cm: out[b,c,j] = feat[b,c,idx[b,j]], feat [B,C,N], idx int32 [B,m] (gather_operation of MDS_module.py); an index
+ *   outside [0,N) yields 0 and sets *bad (bad may be NULL).  spgan_gather_points_cm_bwd: dfeat[b,c,i] = the sum of dout[b,c,j] over the
+ *   slots j with idx[b,j] == i in ascending j, from spgan_gather_csr(idx as int64 [B,m], S = m) -- duplicates are summed.
+ * ---------------------------------------------------------------------------------------- */
+int spgan_expansion_penalty_fwd(const float* xyz, int B, int n, int primitive_size, float alpha, float* dist, int32_t* assignment,
+                                float* mean_mst_length, float* prim_mean_ws, spgan_stream_t s);
+int spgan_expansion_penalty_bwd(const float* xyz, const float* grad_dist, const int32_t* assignment, int B, int n, float* grad_xyz,
+                                spgan_stream_t s);
+int spgan_minimum_density_sample_needs_ws(int n);
+int spgan_minimum_density_sample(const float* xyz, int B, int n, int npoint, const float* mean_mst_length, int split, int32_t* out,
+                                 float* density_ws, spgan_stream_t s);
+int spgan_gather_points_cm(const float* feat, const int32_t* idx, int B, int C, int N, int m, float* out, int32_t* bad, spgan_stream_t s);
+int spgan_gather_points_cm_bwd(const float* dout, const int32_t* rowptr, const int32_t* src, int B, int C, int N, int m, float* dfeat,
+                               spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

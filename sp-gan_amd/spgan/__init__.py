@@ -16,6 +16,8 @@ from .modules import (bilateral_block, bilateral_block_l1, bilateral_block_l2, b
 from .modules import Attention, PointTransformerLayer, Self_Attn            # noqa: F401
 from .modules import Dense_Attn, DenseEdgeModule, DenseModule1D, get_graph_feature            # noqa: F401
 from .modules import Dense_Attn_2D, DenseModule2D, GC_attn, MultiDenseMLP, Self_Attn2                                        # noqa: F401
+from .expansion_penalty import expansionPenaltyFunction, expansionPenaltyModule   # noqa: F401
+from .mds import gather_operation, minimum_density_sample                       # noqa: F401
 from .optim import EMA, Adam, StepLR, flatten_module                       # noqa: F401
 from .parallel import DataParallel, init_process_group_from_env, shard_batch   # noqa: F401
 from .train import TrainStep, requires_grad                                # noqa: F401
@@ -24,4 +26,5 @@ __all__ = ["Generator", "Discriminator", "EdgeBlock", "AdaptivePointNorm", "get_
            "deform_edgeConv_first", "deform_edgeConv_feat", "deform_edgeConv", "bilateral_upsample_edgeConv", "bilateral_block", "bilateral_block_l1",
            "bilateral_block_l2", "bilateral_block_l3", "bilateral_block_l4", "deform_block_middle", "deform_block_tail", "deform_block_feat_middle",
            "deform_block_feat", "PointTransformerLayer", "Attention", "Self_Attn", "Self_Attn2", "DenseEdgeModule", "DenseModule1D", "Dense_Attn", "GC_attn", "DenseModule2D", "MultiDenseMLP", "Dense_Attn_2D", "get_graph_feature", "dis_loss", "gen_loss",
+           "expansionPenaltyFunction", "expansionPenaltyModule", "minimum_density_sample", "gather_operation",
            "GradientPenalty", "TrainStep", "CapturedBody", "Adam", "EMA", "StepLR", "DataParallel", "requires_grad", "ops", "fixture_rng", "sampling"]

@@ -395,6 +395,12 @@ SIGNATURES = {
     "spgan_gc_attn_apply_fwd": (I, [P, I, LG, I, I, LG, P, P, P, LG, P]),
     "spgan_gc_attn_bwd_reduce": (I, [P, LG, P, LG, I, I, I, LG, P, P, P, P]),
     "spgan_gc_attn_bwd_apply": (I, [P, LG, P, LG, I, I, I, LG, P, P, P, P, P, P, P, LG, P, P]),
+    "spgan_expansion_penalty_fwd": (I, [P, I, I, I, F, P, P, P, P, P]),
+    "spgan_expansion_penalty_bwd": (I, [P, P, P, I, I, P, P]),
+    "spgan_minimum_density_sample_needs_ws": (I, [I]),
+    "spgan_minimum_density_sample": (I, [P, I, I, I, P, I, P, P, P]),
+    "spgan_gather_points_cm": (I, [P, P, I, I, I, I, P, P, P]),
+    "spgan_gather_points_cm_bwd": (I, [P, P, P, I, I, I, I, P, P]),
 }
 
 _lib = None
