@@ -219,7 +219,8 @@ int spgan_gemm_nt_uses_w_image(const spgan_gemm_nt_args* a);
 /* pooled[b,c] = max_n lrelu(scale[c]*y[b*rows+n, c] + shift[c], slope) from the tile partials above (rows % 128 == 0, so
  * that no tile straddles two shapes): scale >= 0 takes the tile maxima, scale < 0 the minima.  argmax = global row,
  * yarg = the pre-BatchNorm value there.  Ties go to the lowest row of equal PRE-activation values; scale == 0 (all rows tie):
- * argmax = the first row like torch.max, yarg = the column maximum (y at the first row is not available without Y). */
+ * argmax = the first row like torch.max, yarg = the column maximum (y at the first row is not in the records:
+ * spgan_pool_zero_scale_yarg below puts it there). */
 int spgan_pool_finalize(const float* pool_val, const int32_t* pool_arg, int B, int rows, int C, const float* scale, const float* shift,
                         float slope, float* pooled, int32_t* argmax, float* yarg, spgan_stream_t s);
 /* The same for B = groups * shapes_per_group shapes that belong to `groups` passes with their own BatchNorm: scale / shift are
@@ -228,6 +229,13 @@ int spgan_pool_finalize(const float* pool_val, const int32_t* pool_arg, int B, i
 int spgan_pool_finalize_groups(const float* pool_val, const int32_t* pool_arg, int B, int rows, int C, const float* scale, const float* shift,
                                int group_stride, int shapes_per_group, float slope, float* pooled, int32_t* argmax, float* yarg,
                                int relative_rows, spgan_stream_t s);
+/* Behind either of the two: yarg[b,c] = y[b*rows, c] = prologue(A[b*rows]) . W[c] + bias[c] for every column whose scale is exactly 0 (the
+ * row argmax names there), formed from the GEMM's own operands in fp32 -- the value of Y at that row up to the summation order, exactly it
+ * where the products are exact.  Other columns are left alone.  A [B*rows, K], W [N, K]; p_scale / p_shift / p_slope / p_group_rows as in
+ * spgan_gemm_nt_args (NULL: plain operand); scale [C] (shapes_per_group == 0) or [groups, group_stride] as in spgan_pool_finalize_groups. */
+int spgan_pool_zero_scale_yarg(const float* A, int lda, const float* W, int ldw, const float* bias, const float* p_scale, const float* p_shift,
+                               float p_slope, int p_group_rows, int B, int rows, int N, int K, const float* scale, int group_stride,
+                               int shapes_per_group, float* yarg, spgan_stream_t s);
 
 typedef struct spgan_gemm_tn_args {
   /* C[Na,Nb] = beta*C + sum_m A[m,Na]^T . prologue(B)[m,Nb]  -- weight gradients (reduction over points/edges).

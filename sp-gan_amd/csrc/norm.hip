@@ -70,14 +70,51 @@ __global__ __launch_bounds__(256) void colpartials_kernel(const float* __restric
 // times the workgroups and a quarter of the serial record loop per thread (27 -> ~10 us at 5120 x 128).
 // (the geometry is a template parameter of colfinalize_t_kernel; launch_colfinalize picks it)
 
+// Chan's merge of (count, mean, M2).  Every multiply-add is spelled out and nothing else may be fused: left to the compiler, the
+// contraction of a + d*q differed from call site to call site (fused multiply-adds everywhere in colfinalize_body except at ONE level of
+// its LDS tree, another mix in the grouped kernel), so kernels that promise the same bits for the same records did not give them
+// (tests/test_norm_edges_gpu.py::test_finalize_bn_groups_is_the_sequence_of_single_calls).  FUSED = false is that one tree level
+// (chan_merge_tree: w == 8, in both geometries).  It is kept the way it used to be compiled because the training goldens were recorded
+// with colfinalize_body's bits, and a step's loss moves by more than its bound with the last bit of a BatchNorm statistic.
+template <bool FUSED>
 __device__ __forceinline__ void chan_merge(float& n, float& a, float& b, float n2, float a2, float b2) {
+#pragma clang fp contract(off)
   const float nn = n + n2;
   if (nn > 0.f) {
     const float d = a2 - a;
-    a = a + d * (n2 / nn);
-    b = b + b2 + d * d * (n * n2 / nn);
+    if (FUSED) {
+      a = fmaf(d, n2 / nn, a);
+      b = fmaf(d * d, n * n2 / nn, b + b2);
+    } else {
+      a = a + d * (n2 / nn);
+      b = (b + b2) + (d * d) * (n * n2 / nn);
+    }
   }
   n = nn;
+}
+__device__ __forceinline__ void chan_merge_tree(int w, float& n, float& a, float& b, float n2, float a2, float b2) {
+  if (w == 8) chan_merge<false>(n, a, b, n2, a2, b2);  // the one level with separately rounded products: see above
+  else chan_merge<true>(n, a, b, n2, a2, b2);
+}
+
+// The train-mode BatchNorm bookkeeping of one channel, shared by bn_prepare_kernel and the tails of the finalize kernels (same bits
+// wherever it runs: nothing is left to the compiler's contraction, as in chan_merge).  unb: the unbiased variance the running statistics take.
+__device__ __forceinline__ void bn_advance_running(float* rm, float* rv, float mean, float unb, float momentum) {
+#pragma clang fp contract(off)
+  const float keep = 1.f - momentum;
+  *rm = keep * *rm + momentum * mean;
+  *rv = keep * *rv + momentum * unb;
+}
+
+__device__ __forceinline__ void bn_scale_shift(float mean, float var, float eps, float ga, float be, float* scale, float* shift, float* invstd,
+                                               float* mean_out) {
+#pragma clang fp contract(off)
+  const float inv = 1.0f / sqrtf(var + eps);
+  const float sc = ga * inv;
+  *scale = sc;
+  *shift = fmaf(-mean, sc, be);
+  *invstd = inv;
+  *mean_out = mean;
 }
 
 // Optional tail of the finalize kernel: train-mode BatchNorm bookkeeping from the just-computed (mean, var)
@@ -131,7 +168,7 @@ __device__ __forceinline__ void colfinalize_body(const float* __restrict__ part,
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const float nb = (float)min(tile_rows, G - (t + u * FS) * tile_rows);
-          chan_merge(n, a, b, nb, q[u].x / nb, q[u].y);
+          chan_merge<true>(n, a, b, nb, q[u].x / nb, q[u].y);
         }
       } else {
         a += ((q[0].x + q[1].x) + (q[2].x + q[3].x)) + ((q[4].x + q[5].x) + (q[6].x + q[7].x));
@@ -142,10 +179,10 @@ __device__ __forceinline__ void colfinalize_body(const float* __restrict__ part,
       const float2 p0 = base[(size_t)t * C], p1 = base[(size_t)(t + FS) * C], p2 = base[(size_t)(t + 2 * FS) * C],
                    p3 = base[(size_t)(t + 3 * FS) * C];
       if (mode == 0) {
-        chan_merge(n, a, b, (float)min(tile_rows, G - t * tile_rows), p0.x / (float)min(tile_rows, G - t * tile_rows), p0.y);
-        chan_merge(n, a, b, (float)min(tile_rows, G - (t + FS) * tile_rows), p1.x / (float)min(tile_rows, G - (t + FS) * tile_rows), p1.y);
-        chan_merge(n, a, b, (float)min(tile_rows, G - (t + 2 * FS) * tile_rows), p2.x / (float)min(tile_rows, G - (t + 2 * FS) * tile_rows), p2.y);
-        chan_merge(n, a, b, (float)min(tile_rows, G - (t + 3 * FS) * tile_rows), p3.x / (float)min(tile_rows, G - (t + 3 * FS) * tile_rows), p3.y);
+        chan_merge<true>(n, a, b, (float)min(tile_rows, G - t * tile_rows), p0.x / (float)min(tile_rows, G - t * tile_rows), p0.y);
+        chan_merge<true>(n, a, b, (float)min(tile_rows, G - (t + FS) * tile_rows), p1.x / (float)min(tile_rows, G - (t + FS) * tile_rows), p1.y);
+        chan_merge<true>(n, a, b, (float)min(tile_rows, G - (t + 2 * FS) * tile_rows), p2.x / (float)min(tile_rows, G - (t + 2 * FS) * tile_rows), p2.y);
+        chan_merge<true>(n, a, b, (float)min(tile_rows, G - (t + 3 * FS) * tile_rows), p3.x / (float)min(tile_rows, G - (t + 3 * FS) * tile_rows), p3.y);
       } else {
         a += (p0.x + p1.x) + (p2.x + p3.x);
         b += (p0.y + p1.y) + (p2.y + p3.y);
@@ -155,7 +192,7 @@ __device__ __forceinline__ void colfinalize_body(const float* __restrict__ part,
       const float2 p0 = base[(size_t)t * C];
       if (mode == 0) {
         const float nb = (float)min(tile_rows, G - t * tile_rows);
-        chan_merge(n, a, b, nb, p0.x / nb, p0.y);
+        chan_merge<true>(n, a, b, nb, p0.x / nb, p0.y);
       } else {
         a += p0.x;
         b += p0.y;
@@ -167,7 +204,7 @@ __device__ __forceinline__ void colfinalize_body(const float* __restrict__ part,
   for (int w = FS / 2; w > 0; w >>= 1) {
     if (sl < w) {
       const float n2 = sn[sl + w][cl], a2 = sa[sl + w][cl], b2 = sb[sl + w][cl];
-      if (mode == 0) chan_merge(n, a, b, n2, a2, b2);
+      if (mode == 0) chan_merge_tree(w, n, a, b, n2, a2, b2);
       else { a += a2; b += b2; }
       sn[sl][cl] = n; sa[sl][cl] = a; sb[sl][cl] = b;
     }
@@ -212,17 +249,10 @@ __device__ __forceinline__ void colfinalize_body(const float* __restrict__ part,
       const float* bet = second ? bn.beta2 : bn.beta;
       if (rm) {
         const float cnt = (float)G * (float)(bn.count_rep > 1 ? bn.count_rep : 1);
-        const float unb = cnt > 1.f ? var * (cnt / (cnt - 1.f)) : var;
-        rm[cc] = (1.f - bn.momentum) * rm[cc] + bn.momentum * a;
-        rv[cc] = (1.f - bn.momentum) * rv[cc] + bn.momentum * unb;
+        bn_advance_running(rm + cc, rv + cc, a, cnt > 1.f ? var * (cnt / (cnt - 1.f)) : var, bn.momentum);
       }
-      const float inv = 1.0f / sqrtf(var + bn.eps);
-      const float ga = gam ? gam[cc] : 1.f, be = bet ? bet[cc] : 0.f;
-      const float sc = ga * inv;
-      bn.scale[goff + c] = sc;
-      bn.shift[goff + c] = be - a * sc;
-      bn.invstd[goff + c] = inv;
-      bn.mean_out[goff + c] = a;
+      bn_scale_shift(a, var, bn.eps, gam ? gam[cc] : 1.f, bet ? bet[cc] : 0.f, bn.scale + goff + c, bn.shift + goff + c, bn.invstd + goff + c,
+                     bn.mean_out + goff + c);
     }
   }
   }
@@ -281,7 +311,7 @@ __global__ __launch_bounds__(256) void colfinalize_bn_groups_kernel(const float*
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const float nb = (float)min(tile_rows, G - (t + u * FS) * tile_rows);
-          chan_merge(n[g], a[g], b[g], nb, q[g][u].x / nb, q[g][u].y);
+          chan_merge<true>(n[g], a[g], b[g], nb, q[g][u].x / nb, q[g][u].y);
         }
     }
     for (; t < tiles_per_group; t += FS) {
@@ -290,7 +320,7 @@ __global__ __launch_bounds__(256) void colfinalize_bn_groups_kernel(const float*
       for (int g = 0; g < NG; ++g) q[g] = base[g * gstride + (size_t)t * C];
       const float nb = (float)min(tile_rows, G - t * tile_rows);
 #pragma unroll
-      for (int g = 0; g < NG; ++g) chan_merge(n[g], a[g], b[g], nb, q[g].x / nb, q[g].y);
+      for (int g = 0; g < NG; ++g) chan_merge<true>(n[g], a[g], b[g], nb, q[g].x / nb, q[g].y);
     }
   }
 #pragma unroll
@@ -300,7 +330,7 @@ __global__ __launch_bounds__(256) void colfinalize_bn_groups_kernel(const float*
     if (sl < w) {
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
-        chan_merge(n[g], a[g], b[g], sn[g][sl + w][cl], sa[g][sl + w][cl], sb[g][sl + w][cl]);
+        chan_merge_tree(w, n[g], a[g], b[g], sn[g][sl + w][cl], sa[g][sl + w][cl], sb[g][sl + w][cl]);
         sn[g][sl][cl] = n[g]; sa[g][sl][cl] = a[g]; sb[g][sl][cl] = b[g];
       }
     }
@@ -313,17 +343,10 @@ __global__ __launch_bounds__(256) void colfinalize_bn_groups_kernel(const float*
       const float mean = a[g], var = b[g] / (float)G;
       if (bn.rmean) {
         const float cnt = (float)G;
-        const float unb = cnt > 1.f ? var * (cnt / (cnt - 1.f)) : var;
-        bn.rmean[c] = (1.f - bn.momentum) * bn.rmean[c] + bn.momentum * mean;
-        bn.rvar[c] = (1.f - bn.momentum) * bn.rvar[c] + bn.momentum * unb;
+        bn_advance_running(bn.rmean + c, bn.rvar + c, mean, cnt > 1.f ? var * (cnt / (cnt - 1.f)) : var, bn.momentum);
       }
-      const float inv = 1.0f / sqrtf(var + bn.eps);
-      const float ga = bn.gamma ? bn.gamma[c] : 1.f, be = bn.beta ? bn.beta[c] : 0.f;
-      const float sc = ga * inv;
-      bn.scale[goff + c] = sc;
-      bn.shift[goff + c] = be - mean * sc;
-      bn.invstd[goff + c] = inv;
-      bn.mean_out[goff + c] = mean;
+      bn_scale_shift(mean, var, bn.eps, bn.gamma ? bn.gamma[c] : 1.f, bn.beta ? bn.beta[c] : 0.f, bn.scale + goff + c, bn.shift + goff + c,
+                     bn.invstd + goff + c, bn.mean_out + goff + c);
     }
   }
 }
@@ -345,22 +368,12 @@ __global__ void bn_prepare_kernel(const float* mean, const float* var, const flo
   if (training) {
     m = mean[c];
     v = fmaxf(var[c], 0.f);  // a variance obtained as a difference (d_advance_running_stats) may round below zero
-    if (rmean) {
-      const float unb = count > 1 ? v * ((float)count / (float)(count - 1)) : v;
-      rmean[c] = (1.f - momentum) * rmean[c] + momentum * m;
-      rvar[c] = (1.f - momentum) * rvar[c] + momentum * unb;
-    }
+    if (rmean) bn_advance_running(rmean + c, rvar + c, m, count > 1 ? v * ((float)count / (float)(count - 1)) : v, momentum);
   } else {
     m = rmean[c];
     v = rvar[c];
   }
-  const float inv = 1.0f / sqrtf(v + eps);
-  const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-  const float sc = g * inv;
-  scale[c] = sc;
-  shift[c] = b - m * sc;
-  invstd[c] = inv;
-  mean_used[c] = m;
+  bn_scale_shift(m, v, eps, gamma ? gamma[c] : 1.f, beta ? beta[c] : 0.f, scale + c, shift + c, invstd + c, mean_used + c);
 }
 
 __global__ void bn_bwd_apply_kernel(const float* __restrict__ g, const float* __restrict__ y, int ld, size_t M, int C,
@@ -529,7 +542,42 @@ __global__ void pool_finalize_kernel(const float* __restrict__ pv, const int32_t
   if (yarg) yarg[(size_t)b * C + c] = best;
 }
 
+// spgan_pool_zero_scale_yarg: a column whose BatchNorm scale is exactly 0 ties in every row, pool_finalize_kernel reports row b*rows for it,
+// and the (max, min) records hold no value of that row.  One thread per (shape, column) forms y[b*rows, c] = prologue(A[b*rows]) . W[c] +
+// bias[c] itself; every other column returns at once (in training no scale is 0: the launch is a few empty wavefronts).
+__global__ void pool_zero_scale_yarg_kernel(const float* __restrict__ A, int lda, const float* __restrict__ W, int ldw, const float* __restrict__ bias,
+                                            const float* __restrict__ p_scale, const float* __restrict__ p_shift, float p_slope, int p_group_rows,
+                                            int rows, int N, int K, const float* __restrict__ scale, int group_stride, int shapes_per_group,
+                                            float* __restrict__ yarg) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (c >= N) return;
+  const int grp = shapes_per_group > 0 ? b / shapes_per_group : 0;
+  if (scale[(size_t)grp * group_stride + c] != 0.f) return;
+  const size_t row = (size_t)b * rows;
+  const float* a = A + row * lda;
+  const float* w = W + (size_t)c * ldw;
+  const size_t po = p_group_rows > 0 ? (row / p_group_rows) * (size_t)K : 0;
+  float acc = 0.f;
+  for (int k = 0; k < K; ++k) {
+    float v = a[k];
+    if (p_scale) v = lrelu_f(fmaf(v, p_scale[po + k], p_shift[po + k]), p_slope);
+    acc = fmaf(v, w[k], acc);
+  }
+  yarg[(size_t)b * N + c] = acc + (bias ? bias[c] : 0.f);
+}
+
 }  // namespace
+
+extern "C" int spgan_pool_zero_scale_yarg(const float* A, int lda, const float* W, int ldw, const float* bias, const float* p_scale,
+                                          const float* p_shift, float p_slope, int p_group_rows, int B, int rows, int N, int K, const float* scale,
+                                          int group_stride, int shapes_per_group, float* yarg, spgan_stream_t s_) {
+  SPGAN_CHECK_ARG(A && W && scale && yarg && B > 0 && rows > 0 && N > 0 && K > 0 && lda >= K && ldw >= K);
+  SPGAN_CHECK_ARG((p_scale == nullptr) == (p_shift == nullptr) && p_group_rows >= 0 && shapes_per_group >= 0 && group_stride >= 0);
+  SPGAN_CHECK_ARG(shapes_per_group == 0 || (B % shapes_per_group == 0 && group_stride >= N));
+  hipLaunchKernelGGL(pool_zero_scale_yarg_kernel, dim3(cdiv(N, 64), B), dim3(64), 0, (hipStream_t)s_, A, lda, W, ldw, bias, p_scale, p_shift, p_slope,
+                     p_group_rows, rows, N, K, scale, group_stride, shapes_per_group, yarg);
+  return spgan_launch_status();
+}
 
 extern "C" int spgan_pool_finalize(const float* pool_val, const int32_t* pool_arg, int B, int rows, int C, const float* scale, const float* shift,
                                    float slope, float* pooled, int32_t* argmax, float* yarg, spgan_stream_t s_) {

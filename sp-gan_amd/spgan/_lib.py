@@ -194,6 +194,7 @@ SIGNATURES = {
     "spgan_gemm_nt_owns_columns": (I, [C.POINTER(GemmNTArgs)]),
     "spgan_pool_finalize": (I, [P, P, I, I, I, P, P, F, P, P, P, P]),
     "spgan_pool_finalize_groups": (I, [P, P, I, I, I, P, P, I, I, F, P, P, P, I, P]),
+    "spgan_pool_zero_scale_yarg": (I, [P, I, P, I, P, P, P, F, I, I, I, I, I, P, I, I, P, P]),
     "spgan_gemm_tn_ws_bytes": (SZ, [I, I, I]),
     "spgan_gemm_tn_ws_bytes_lp": (SZ, [I, I, I, I]),
     "spgan_gemm_tn_splits_lp": (I, [I, I, I, I]),

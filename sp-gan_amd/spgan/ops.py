@@ -1558,7 +1558,8 @@ def gemm_bn_pool(A: Tensor, W: Tensor, bias: Optional[Tensor], bn, rows: int, sl
     itself is only written when keep_y.  bn = (gamma, beta, running_mean | None, running_var | None).
     before_finalize: a callable issued between the GEMM launch and the finalize launches (which update the running statistics) -- for a
     caller that has to advance the same running statistics with ANOTHER pass first but wants this GEMM to follow its producer directly.
-    Returns (Y | None, (scale, shift, invstd, mean), pooled [B,C], argmax int32 [B,C] (global rows), yarg [B,C])."""
+    Returns (Y | None, (scale, shift, invstd, mean), pooled [B,C], argmax int32 [B,C] (global rows), yarg [B,C] = y at those rows; for a
+    column whose scale is exactly 0 -- every row ties, argmax names the shape's first row -- a third small launch forms y there)."""
     _rowmajor2d(A, "A"); _rowmajor2d(W, "W")
     N, K = W.shape
     M_ = A.shape[0]
@@ -1599,6 +1600,8 @@ def gemm_bn_pool(A: Tensor, W: Tensor, bias: Optional[Tensor], bn, rows: int, sl
     arg = torch.empty((B, N), dtype=torch.int32, device=dev)
     check(lib.spgan_pool_finalize(_p(pval), _p(parg), B, rows, N, _p(st[0]), _p(st[1]), float(slope), _p(pooled), _p(arg), _p(yarg), _s()),
           "pool_finalize", B=B, rows=rows, C=N)
+    check(lib.spgan_pool_zero_scale_yarg(a.A, a.lda, a.W, a.ldw, a.bias, a.p_scale, a.p_shift, a.p_slope, 0, B, rows, N, K, _p(st[0]), 0, 0, _p(yarg), _s()),
+          "pool_zero_scale_yarg", B=B, rows=rows, C=N)
     return Y, (st[0], st[1], st[2], st[3]), pooled, arg, yarg
 
 
@@ -1665,6 +1668,8 @@ def gemm_bn_groups(A: Tensor, W: Tensor, bias: Optional[Tensor], bn, groups: int
     arg = torch.empty((B, N), dtype=torch.int32, device=dev)
     check(lib.spgan_pool_finalize_groups(_p(pval), _p(parg), B, rows, N, _p(out[0]), _p(out[1]), N, Mg // rows, float(slope),
                                          _p(pooled), _p(arg), _p(yarg), 1, _s()), "pool_finalize_groups", B=B, rows=rows, C=N)
+    check(lib.spgan_pool_zero_scale_yarg(a.A, a.lda, a.W, a.ldw, a.bias, a.p_scale, a.p_shift, a.p_slope, a.p_group_rows if pro is not None else 0,
+                                         B, rows, N, K, _p(out[0]), N, Mg // rows, _p(yarg), _s()), "pool_zero_scale_yarg", B=B, rows=rows, C=N)
     return out, pooled, arg, yarg
 
 
