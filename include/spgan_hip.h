@@ -1291,6 +1291,57 @@ int spgan_gather_points_cm(const float* feat, const int32_t* idx, int B, int C, 
 int spgan_gather_points_cm_bwd(const float* dout, const int32_t* rowptr, const int32_t* src, int B, int C, int N, int m, float* dfeat,
                                spgan_stream_t s);
 
+/* ----------------------------------------------------------------------------------------
+ * The pointops extension (metrics/pointops/src of the reference; csrc/pointops.hip).  Every index tensor is int32.  Every
+ * squared distance is d2 = (dx*dx + dy*dy) + dz*dz with dx = query - candidate, each operation rounded on its own.  `bad` may be NULL.
+ * spgan_pointops_knnquery: xyz [B,n,3], new_xyz [B,m,3], 1 <= nsample <= 200 -> idx [B,m,nsample], dist2 [B,m,nsample]: ascending d2, the
+ *   lower index first on equal d2, the query itself included when it is a cloud point; slots past n hold index 0 and +inf.  Clouds of up to
+ *   spgan_pointops_knn_capacity() points are selected from registers in one pass, larger ones in chunks of that size (any n >= 1).
+ * spgan_pointops_nearestneighbor: the three nearest known [B,m,3] of every unknown [B,n,3] (the same kernel, nsample = 3) -> dist2, idx
+ *   [B,n,3]; the caller takes the square root.
+ * spgan_pointops_ballquery: the first nsample indices (ascending) with d2 < radius*radius (STRICT; a float product), every slot pre-filled
+ *   with the first hit, all zeros for an empty ball.
+ * spgan_pointops_labelstat_ballrange: new_label_stat[b,j,:] = the sum of label_stat[b,k,:] (int32 [B,n,nclass]) over ALL k with d2 < r*r.
+ * spgan_pointops_labelstat_and_ballquery: the ball query, and the sum over the hits it returns only (the scan ends at nsample hits).
+ * spgan_pointops_labelstat_idx: the sum of the rows named by idx [B,m,nsample]; an index outside [0,n) adds nothing and sets *bad.
+ * spgan_pointops_featuredistribute: for every xyz [B,m,3] the index of the nearest max_xyz [B,n,3], the lowest index among equals, -1 when
+ *   no d2 is below 100000 (the reference's starting value).
+ * spgan_pointops_group_cm: out[b, c0+c, j, k] = src[b, c, idx[b,j,k]] for c < C into the channel slice [c0, c0+C) of out [B,Ctot,m,K]; src is
+ *   [B,C,n], or with point_major != 0 [B,n,3] (C = 3); center [B,m,3] (C = 3), when given, is subtracted.  An index outside [0,n) writes 0
+ *   and sets *bad.  Clouds of up to spgan_pointops_group_stage_limit() points are staged in LDS.
+ * spgan_pointops_group_cm_bwd: dsrc[b,c,i] = the sum of dout[b, c0+c, s] over the slots s with idx[b,s] == i in ascending s, from
+ *   spgan_gather_csr(idx as int64 [B, m*K]) (dsrc in src's layout; NULL skips it); dcenter[b,j,c] = -(sum over k ascending of
+ *   dout[b, c0+c, j, k]) (NULL skips it).
+ * spgan_pointops_group_int: out[b,c,j,k] = feat[b,c,idx[b,j,k]] on int64 features (grouping_int).
+ * spgan_pointops_interpolate_cm: out[b,c,j] = (w0*f0 + w1*f1) + w2*f2, f_t = feat[b,c,idx[b,j,t]]; feat [B,C,m], idx / weight [B,n,3].
+ * spgan_pointops_interpolate_cm_bwd: dfeat[b,c,i] = the sum over the slots e of (b,i) in ascending e (spgan_gather_csr of idx as int64
+ *   [B, n*3]) of weight[e] * dout[b,c,e/3 - b*n].
+ * ---------------------------------------------------------------------------------------- */
+int spgan_pointops_knn_capacity(void);
+int spgan_pointops_group_stage_limit(void);
+int spgan_pointops_knnquery(const float* xyz, const float* new_xyz, int B, int n, int m, int nsample, int32_t* idx, float* dist2,
+                            spgan_stream_t s);
+int spgan_pointops_nearestneighbor(const float* unknown, const float* known, int B, int n, int m, float* dist2, int32_t* idx, spgan_stream_t s);
+int spgan_pointops_ballquery(float radius, int nsample, const float* xyz, const float* new_xyz, int B, int n, int m, int32_t* idx,
+                             spgan_stream_t s);
+int spgan_pointops_labelstat_ballrange(float radius, const float* xyz, const float* new_xyz, const int32_t* label_stat, int B, int n, int m,
+                                       int nclass, int32_t* new_label_stat, spgan_stream_t s);
+int spgan_pointops_labelstat_and_ballquery(float radius, int nsample, const float* xyz, const float* new_xyz, const int32_t* label_stat, int B,
+                                           int n, int m, int nclass, int32_t* idx, int32_t* new_label_stat, spgan_stream_t s);
+int spgan_pointops_labelstat_idx(const int32_t* label_stat, const int32_t* idx, int B, int n, int m, int nsample, int nclass,
+                                 int32_t* new_label_stat, int32_t* bad, spgan_stream_t s);
+int spgan_pointops_featuredistribute(const float* max_xyz, const float* xyz, int B, int n, int m, int32_t* distribute_idx, spgan_stream_t s);
+int spgan_pointops_group_cm(const float* src, int point_major, const float* center, const int32_t* idx, int B, int C, int n, int m, int K,
+                            int c0, int Ctot, float* out, int32_t* bad, spgan_stream_t s);
+int spgan_pointops_group_cm_bwd(const float* dout, const int32_t* rowptr, const int32_t* slots, int B, int C, int n, int m, int K, int c0,
+                                int Ctot, int point_major, float* dsrc, float* dcenter, spgan_stream_t s);
+int spgan_pointops_group_int(const int64_t* feat, const int32_t* idx, int B, int C, int n, int m, int K, int64_t* out, int32_t* bad,
+                             spgan_stream_t s);
+int spgan_pointops_interpolate_cm(const float* feat, const int32_t* idx, const float* weight, int B, int C, int m, int n, float* out,
+                                  int32_t* bad, spgan_stream_t s);
+int spgan_pointops_interpolate_cm_bwd(const float* dout, const float* weight, const int32_t* rowptr, const int32_t* slots, int B, int C, int m,
+                                      int n, float* dfeat, spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

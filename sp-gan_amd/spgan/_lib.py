@@ -402,6 +402,20 @@ SIGNATURES = {
     "spgan_minimum_density_sample": (I, [P, I, I, I, P, I, P, P, P]),
     "spgan_gather_points_cm": (I, [P, P, I, I, I, I, P, P, P]),
     "spgan_gather_points_cm_bwd": (I, [P, P, P, I, I, I, I, P, P]),
+    "spgan_pointops_knn_capacity": (I, []),
+    "spgan_pointops_group_stage_limit": (I, []),
+    "spgan_pointops_knnquery": (I, [P, P, I, I, I, I, P, P, P]),
+    "spgan_pointops_nearestneighbor": (I, [P, P, I, I, I, P, P, P]),
+    "spgan_pointops_ballquery": (I, [F, I, P, P, I, I, I, P, P]),
+    "spgan_pointops_labelstat_ballrange": (I, [F, P, P, P, I, I, I, I, P, P]),
+    "spgan_pointops_labelstat_and_ballquery": (I, [F, I, P, P, P, I, I, I, I, P, P, P]),
+    "spgan_pointops_labelstat_idx": (I, [P, P, I, I, I, I, I, P, P, P]),
+    "spgan_pointops_featuredistribute": (I, [P, P, I, I, I, P, P]),
+    "spgan_pointops_group_cm": (I, [P, I, P, P, I, I, I, I, I, I, I, P, P, P]),
+    "spgan_pointops_group_cm_bwd": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P]),
+    "spgan_pointops_group_int": (I, [P, P, I, I, I, I, I, P, P, P]),
+    "spgan_pointops_interpolate_cm": (I, [P, P, P, I, I, I, I, P, P, P]),
+    "spgan_pointops_interpolate_cm_bwd": (I, [P, P, P, P, I, I, I, I, P, P]),
 }
 
 _lib = None
