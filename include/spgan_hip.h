@@ -1342,6 +1342,37 @@ int spgan_pointops_interpolate_cm(const float* feat, const int32_t* idx, const f
 int spgan_pointops_interpolate_cm_bwd(const float* dout, const float* weight, const int32_t* rowptr, const int32_t* slots, int B, int C, int m,
                                       int n, float* dfeat, spgan_stream_t s);
 
+/* ----------------------------------------------------------------------------------------
+ * Set abstraction with the first MLP layer hoisted onto the points (metrics/pointnet2/pointnet2_modules.py of the reference;
+ * csrc/sa_group.hip).  Indices are int32 and local to their cloud.
+ * spgan_sa_ballquery_multi: the ball queries of up to SPGAN_SA_MAX_SCALES radii around the same centres in one walk of the cloud: xyz
+ *   [B,n,3], new_xyz [B,m,3] -> idx[s] [B,m,nsample[s]], each list equal to spgan_pointops_ballquery(radius[s], nsample[s]) bit for bit.
+ * spgan_sa_gather: Y[(q*K + k), c] = (P[(b*n + idx[q,k]), colp + c] - Qc[q, colq + c]) + bias[c] for q = b*m + j < B*m, k < K, c < C;
+ *   P [B*n, ldp], Qc [B*m, ldq], Y [B*m*K, ldy], bias [C] or NULL.  part [tiles, C, 2] (NULL: none) receives the (sum, centred M2)
+ *   records of Y's columns per tile of spgan_sa_gather_tile_rows(K) rows, as spgan_colstats_finalize / _finalize_bn read them.  An index
+ *   outside [0,n) reads point 0 and sets *bad (bad may be NULL).
+ * spgan_sa_scatter: the gather's backward.  dP[p, colp + c] = the sum of dY[e, c] over the slots e that read point p, in ascending e
+ *   (rowptr [BN,2], src: spgan_gather_csr of the index list as int64 [B, m*K]); dQ[q, colq + c] = -(sum over k ascending of dY[q*K + k, c]).
+ *   dY [Q*K, ld >= C], dP [BN, ldp], dQ [Q, ldq]; dP or dQ may be NULL (not both).
+ * spgan_sa_rows_to_cm_slice: cm[b, c0+c, s] = rows[(b*S + s), c] into the channel slice [c0, c0+C) of cm [B,Ctot,S]; rows [B*S, C].
+ * spgan_sa_cm_slice_to_rows: the inverse (the gradient of the former).
+ * ---------------------------------------------------------------------------------------- */
+#define SPGAN_SA_MAX_SCALES 8
+typedef struct spgan_sa_query_args {
+  int count;
+  float radius[SPGAN_SA_MAX_SCALES];
+  int nsample[SPGAN_SA_MAX_SCALES];
+  int32_t* idx[SPGAN_SA_MAX_SCALES];
+} spgan_sa_query_args;
+int spgan_sa_gather_tile_rows(int K);
+int spgan_sa_ballquery_multi(const spgan_sa_query_args* a, const float* xyz, const float* new_xyz, int B, int n, int m, spgan_stream_t s);
+int spgan_sa_gather(const float* P, int ldp, int colp, const float* Qc, int ldq, int colq, const float* bias, const int32_t* idx, int B, int n,
+                    int m, int K, int C, float* Y, int ldy, float* part, int32_t* bad, spgan_stream_t s);
+int spgan_sa_scatter(const float* dY, int ld, int C, const int32_t* rowptr, const int32_t* src, int BN, float* dP, int ldp, int colp, int Q, int K,
+                     float* dQ, int ldq, int colq, spgan_stream_t s);
+int spgan_sa_rows_to_cm_slice(const float* rows, int B, int S, int C, int c0, int Ctot, float* cm, spgan_stream_t s);
+int spgan_sa_cm_slice_to_rows(const float* cm, int B, int S, int C, int c0, int Ctot, float* rows, spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

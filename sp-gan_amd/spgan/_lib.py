@@ -168,6 +168,15 @@ class GcBranch(C.Structure):
     _fields_ = [("W1", C.c_void_p), ("b1", C.c_void_p), ("lnw", C.c_void_p), ("lnb", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p)]
 
 
+SA_MAX_SCALES = 8       # SPGAN_SA_MAX_SCALES: radii per multi-radius ball query
+
+
+class SaQueryArgs(C.Structure):
+    """spgan_sa_query_args"""
+    _fields_ = [("count", C.c_int), ("radius", C.c_float * SA_MAX_SCALES), ("nsample", C.c_int * SA_MAX_SCALES),
+                ("idx", C.c_void_p * SA_MAX_SCALES)]
+
+
 I, F, P, SZ = C.c_int, C.c_float, C.c_void_p, C.c_size_t
 LG, GCB = C.c_long, C.POINTER(GcBranch)
 
@@ -416,6 +425,12 @@ SIGNATURES = {
     "spgan_pointops_group_int": (I, [P, P, I, I, I, I, I, P, P, P]),
     "spgan_pointops_interpolate_cm": (I, [P, P, P, I, I, I, I, P, P, P]),
     "spgan_pointops_interpolate_cm_bwd": (I, [P, P, P, P, I, I, I, I, P, P]),
+    "spgan_sa_gather_tile_rows": (I, [I]),
+    "spgan_sa_ballquery_multi": (I, [C.POINTER(SaQueryArgs), P, P, I, I, I, P]),
+    "spgan_sa_gather": (I, [P, I, I, P, I, I, P, P, I, I, I, I, I, P, I, P, P, P]),
+    "spgan_sa_scatter": (I, [P, I, I, P, P, I, P, I, I, I, I, P, I, I, P]),
+    "spgan_sa_rows_to_cm_slice": (I, [P, I, I, I, I, I, P, P]),
+    "spgan_sa_cm_slice_to_rows": (I, [P, I, I, I, I, I, P, P]),
 }
 
 _lib = None

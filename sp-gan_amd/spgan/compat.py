@@ -6,6 +6,8 @@
     from pointops import pointops_util               # Common/loss_utils.py:13        -> spgan.pointops
     from CD_EMD.emd_ import emd_module               # Common/loss_utils.py:20        -> spgan.metrics (emdModule, emdFunction)
     from CD_EMD.cd.chamferdist import ChamferDistance as CD                           # -> spgan.metrics.ChamferDistance
+    from pointnet2.pointnet2_modules import PointnetSAModule, PointnetSAModuleMSG     # model.py / Generator.py / modules.py (commented there)
+    from metrics.pointnet2 import pointnet2_utils, pytorch_utils                      # -> spgan.pointnet2_utils, spgan.pytorch_utils
 
 `install()` puts lightweight module objects into sys.modules; each forwards attribute look-ups to the spgan module behind it, so the names
 resolve to the very objects of this package.  A name that already resolves to a real module (one in sys.modules, or one the import system
@@ -39,6 +41,19 @@ STAND_INS: Dict[str, Optional[str]] = {
     "CD_EMD.cd.chamferdist.ChamferDistance": "spgan.metrics",
     "expansion_penalty_module": "spgan.expansion_penalty",
     "MDS_module": "spgan.mds",
+    "pointnet2": None,
+    "pointnet2.pointnet2_utils": "spgan.pointnet2_utils",
+    "pointnet2.pointnet2_modules": "spgan.pointnet2_modules",
+    "pointnet2.pytorch_utils": "spgan.pytorch_utils",
+    "metrics.pointnet2": None,
+    "metrics.pointnet2.pointnet2_utils": "spgan.pointnet2_utils",
+    "metrics.pointnet2.pointnet2_modules": "spgan.pointnet2_modules",
+    "metrics.pointnet2.pytorch_utils": "spgan.pytorch_utils",
+    "metrics.pointnet2_ops": None,
+    "metrics.pointnet2_ops.pointnet2_utils": "spgan.pointnet2_utils",
+    "metrics.pointnet2_ops.pointnet2_modules": "spgan.pointnet2_modules",
+    "metrics.pointnet2_ops.pytorch_utils": "spgan.pytorch_utils",
+    "metrics.pointnet2_utils": "spgan.pointnet2_utils",
 }
 # children that are NOT set as attributes of their parent: `from CD_EMD.cd.chamferdist import ChamferDistance` is the class, as the
 # reference's own __init__ arranges
