@@ -542,6 +542,16 @@ int spgan_edge_attend_bwd(const float* dT, const float* h2pre, const float* sc2,
                           const float* inv2, const float* PQR, int ld, int H, int F, const int32_t* idx, int M, int k,
                           const float* bx, const float* scx, const float* shx, const float* meanx, const float* invx,
                           float slope, float* g2, float* gy, float* partials, spgan_stream_t s);
+/* spgan_edge_attend_bwd with dT = dout . WoT^T formed inside the launch (csrc/edge_dt.hip): dout [M, ldo >= F], WoT [k*F, ldw >= F] as
+ * written by spgan_conv_out_weight_pm; dT [M, k*F] never reaches memory.  k = 10, F = 128, M % 32 == 0, fp32, 16-byte aligned dout / WoT
+ * rows only.  g2, gy and the partials are bit for bit those of spgan_gemm_nt (256 x 256-tile kernel) followed by spgan_edge_attend_bwd;
+ * spgan_edge_attend_bwd_dt_selected is 1 exactly when that product would run the 256 x 256-tile kernel (tile_hint as in
+ * spgan_gemm_nt_args; honours SPGAN_NT_WIDE=0), the only case in which the fused launch may replace the pair. */
+int spgan_edge_attend_bwd_dt_selected(const float* dout, int ldo, const float* WoT, int ldw, int M, int k, int F, int tile_hint);
+int spgan_edge_attend_bwd_dt(const float* dout, int ldo, const float* WoT, int ldw, const float* h2pre, const float* sc2, const float* sh2,
+                             const float* mean2, const float* inv2, const float* PQR, int ld, int H, int F, const int32_t* idx, int M, int k,
+                             const float* bx, const float* scx, const float* shx, const float* meanx, const float* invx, float slope,
+                             float* g2, float* gy, float* partials, spgan_stream_t s);
 /* BatchNorm backward of both per-edge pre-activations fused with the reduction onto points (gather over the CSR
  * in-edge lists; the backward obligation of modules.py:708-720): dPQR[M, H+2F]. sums* = [sum g | sum g*xhat]. */
 int spgan_edge_scatter(const float* g1, const float* gy, const float* PQR, int ld, int H, int F, const int32_t* idx,

@@ -13,21 +13,9 @@
 // Thread mapping everywhere: one wave per point, lanes along channels.
 #include <stdlib.h>
 #include "common.hpp"
+#include "edge_attend.hpp"   // xcd_block(), grid8(), the attention backward's per-element arithmetic
 
 namespace {
-
-// XCD-aware workgroup order for the gather kernels: the hardware deals consecutive workgroup ids round-robin to the 8 XCDs, each with its own
-// 4 MB L2.  In launch order, neighbouring point chunks -- which gather the same rows of the [B*N, H+2F] point tensor, 2.6 MB per shape at
-// F = 128 -- would sit on eight different L2s and every shape's rows would be fetched eight times.  Logical block xcd * per + t runs on XCD
-// xcd: an XCD works through a CONTIGUOUS eighth of the points (4 shapes at B = 32), whose rows it fetches once.  Grids are rounded up to a
-// multiple of 8; logical blocks past the end find no points.
-// Measured in the replayed step (profiles/r04_step_sequence.txt): edge_stats 65 -> 43-51 us, edge_attend_bwd 280 -> 272, edge_scatter 237 -> 228
-// (9.24 -> 9.18-9.20 ms/step on one box); the same order changed nothing for the kNN scan and the per-edge-operand GEMM (not kept there).
-__device__ __forceinline__ int xcd_block() {
-  const int per = gridDim.x >> 3;
-  return (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-}
-inline int grid8(long n) { return (int)((n + 7) / 8 * 8); }
 
 // ------------------------------------------------------------------------------------------ weights
 __global__ void edge_wcat_kernel(const float* __restrict__ Ww0, const float* __restrict__ Wx, int H, int F, int C, float* __restrict__ Wcat,
@@ -410,43 +398,8 @@ __global__ __launch_bounds__(256) void edge_attend_bwd_k_kernel(
         }
         float o2[K][VEC], oy[K][VEC];
 #pragma unroll
-        for (int q = 0; q < VEC; ++q) {
-          float e[K], mx = -INFINITY;
-#pragma unroll
-          for (int r = 0; r < K; ++r) {
-            e[r] = lrelu_f(fmaf(hp[r][q], a2[q], c2[q]), slope);
-            mx = fmaxf(mx, e[r]);
-          }
-          float den = 0.f;
-#pragma unroll
-          for (int r = 0; r < K; ++r) {
-            e[r] = expf(e[r] - mx);
-            den += e[r];
-          }
-          const float rden = 1.0f / den;
-          float dot = 0.f;
-#pragma unroll
-          for (int r = 0; r < K; ++r) {
-            yp[r][q] = (Ri[q] + yp[r][q]) + bb[q];
-            e[r] *= rden;
-            const float yv = lrelu_f(fmaf(yp[r][q], ax[q], cx[q]), slope);
-            dot = fmaf(d[r][q] * yv, e[r], dot);
-          }
-#pragma unroll
-          for (int r = 0; r < K; ++r) {
-            const float z2 = fmaf(hp[r][q], a2[q], c2[q]);
-            const float zy = fmaf(yp[r][q], ax[q], cx[q]);
-            const float yv = lrelu_f(zy, slope);
-            const float ds = e[r] * (d[r][q] * yv - dot);
-            const float v2 = ds * lrelu_mask(z2, slope);
-            const float vy = d[r][q] * e[r] * lrelu_mask(zy, slope);
-            o2[r][q] = v2; oy[r][q] = vy;
-            s0[q] += v2;
-            s1[q] = fmaf(v2, (hp[r][q] - m2[q]) * i2[q], s1[q]);
-            s2[q] += vy;
-            s3[q] = fmaf(vy, (yp[r][q] - mxm[q]) * ixv[q], s3[q]);
-          }
-        }
+        for (int q = 0; q < VEC; ++q)   // the arithmetic is shared with edge_dt.hip (edge_attend.hpp): one set of expressions, one set of bits
+          edge_attend_bwd_elem<K, VEC, VEC == 1>(q, hp, d, yp, Ri, a2, c2, ax, cx, bb, m2, i2, mxm, ixv, slope, o2, oy, s0, s1, s2, s3);
 #pragma unroll
         for (int r = 0; r < K; ++r) {
           if (TB) stv_b<VEC>(reinterpret_cast<__bf16*>(g2) + ((size_t)i * K + r) * F + f, o2[r]);   // consumed as a GEMM operand only

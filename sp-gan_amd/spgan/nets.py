@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import adain_epi, ops
+from . import adain_epi, edge_dt, ops
 
 Tensor = torch.Tensor
 NEG = 0.01     # Generator.py:22, Discriminator.py:19
@@ -1111,9 +1111,14 @@ def edgeblock_backward(P, pre: str, ctx, dout: Tensor, csr: Tuple[Tensor, Tensor
     # conv_out
     gwo, g[pre + ".conv_out.bias"] = ops.gemm_tn(dout, ctx["T"], with_colsum=True, defer=True)      # the bias gradient rides along (column sums of dout); both split sums wait for the pass's one reduction launch
     g[pre + ".conv_out.weight"] = conv_out_weight_grad_from_pm(gwo, F_, k)
-    dT = ops.gemm_nt(dout, ctx["WoT"], out_bf16=ctx["T"].dtype == torch.float16)     # [M, k*F]
-    # softmax * conv_x product, both LeakyReLUs
-    g2, gy, sums2, sumsy = ops.edge_attend_bwd(dT, ctx["h2pre"], bn2[0], bn2[1], bn2[3], bn2[2], PQR, idx, bx, bnx[0], bnx[1], bnx[3], bnx[2], NEG)
+    if edge_dt.usable(dout, ctx["WoT"], ctx["T"], ctx["h2pre"], PQR, k, F_):
+        # EdgeConv2 in the fp32 mode: dT [M, k*F] is formed in the accumulators of the launch that consumes it (csrc/edge_dt.hip), bit for bit
+        g2, gy, sums2, sumsy = edge_dt.backward(dout, ctx["WoT"], ctx["h2pre"], bn2[0], bn2[1], bn2[3], bn2[2], PQR, idx, bx, bnx[0], bnx[1],
+                                                bnx[3], bnx[2], NEG)
+    else:
+        dT = ops.gemm_nt(dout, ctx["WoT"], out_bf16=ctx["T"].dtype == torch.float16)     # [M, k*F]
+        # softmax * conv_x product, both LeakyReLUs
+        g2, gy, sums2, sumsy = ops.edge_attend_bwd(dT, ctx["h2pre"], bn2[0], bn2[1], bn2[3], bn2[2], PQR, idx, bx, bnx[0], bnx[1], bnx[3], bnx[2], NEG)
     g[pre + ".conv_w.4.weight"] = sums2[F_:]; g[pre + ".conv_w.4.bias"] = sums2[:F_]
     g[pre + ".conv_x.1.weight"] = sumsy[F_:]; g[pre + ".conv_x.1.bias"] = sumsy[:F_]
     if not ctx["training"]:
