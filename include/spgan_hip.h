@@ -640,8 +640,10 @@ int spgan_index_points(const float* points, const int64_t* idx, int B, int N, in
 /* iterative farthest point sampling from start[b] (NULL: 0); dist_ws: B*N floats   pointnet_util.py:63-84, pointconv_util.py:60-83 */
 int spgan_farthest_point_sample(const float* xyz, int B, int N, int npoint, const int64_t* start, int64_t* out, float* dist_ws,
                                 spgan_stream_t s);
-/* first nsample indices (ascending) with d^2 <= r^2, padded with the first hit     pointnet_util.py:87-107 */
-int spgan_query_ball_point(float radius, int nsample, const float* xyz, const float* new_xyz, int B, int N, int S, int C,
+/* first nsample indices (ascending) with not (d^2 > thr), padded with the first hit (no hit: every slot N).  thr >= 0 is the THRESHOLD on
+ * the squared distance, not the radius: the float32 nearest to the caller's double radius^2, which is what the reference's
+ * `sqrdists > radius ** 2` compares with (squaring a float32 radius is one ulp off for many radii)     pointnet_util.py:87-107 */
+int spgan_query_ball_point(float thr, int nsample, const float* xyz, const float* new_xyz, int B, int N, int S, int C,
                            int64_t* out, spgan_stream_t s);
 /* nsample nearest (self included), ascending (distance, index)                      pointconv_util.py:107-118 */
 int spgan_knn_point(int nsample, const float* xyz, const float* new_xyz, int B, int N, int S, int C, int64_t* out, spgan_stream_t s);

@@ -78,10 +78,13 @@ __global__ __launch_bounds__(512) void fps_kernel(const float* __restrict__ xyz,
   }
 }
 
-// First `nsample` indices (ascending) with d^2 <= r^2, padded with the first hit      pointnet_util.py:87-107
+// First `nsample` indices (ascending) that are not masked by the reference's `sqrdists > radius ** 2`, padded with the first hit
+// (pointnet_util.py:87-107).  thr is the float32 that torch compares the float32 distances with there: the Python double radius ** 2
+// rounded to float32 -- formed on the host from the caller's double; squaring a float32 radius lands one ulp beside it for about a
+// third of the two-decimal radii (0.05, 0.1, 0.2, 0.4, 0.8 above; 0.35, 0.45, 0.7, 0.9 below).
 template <int C>
 __global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict__ xyz, const float* __restrict__ new_xyz, int N, int S,
-                                                         float r2, int nsample, int64_t* __restrict__ out) {
+                                                         float thr, int nsample, int64_t* __restrict__ out) {
   constexpr int TC = 256;
   __shared__ float cand[TC * C];
   __shared__ float cn[TC];
@@ -107,7 +110,7 @@ __global__ __launch_bounds__(256) void ball_query_kernel(const float* __restrict
     if (ok && cnt < nsample)
       for (int j = 0; j < nc && cnt < nsample; ++j) {
         const float d = sqdist_expanded<C>(q, qn, cand + j * C, cn[j]);
-        if (!(d > r2)) {
+        if (!(d > thr)) {
           if (cnt == 0) first = c0 + j;
           o[cnt++] = c0 + j;
         }
@@ -329,13 +332,12 @@ extern "C" int spgan_farthest_point_sample(const float* xyz, int B, int N, int n
   return spgan_launch_status();
 }
 
-extern "C" int spgan_query_ball_point(float radius, int nsample, const float* xyz, const float* new_xyz, int B, int N, int S, int C,
+extern "C" int spgan_query_ball_point(float thr, int nsample, const float* xyz, const float* new_xyz, int B, int N, int S, int C,
                                       int64_t* out, spgan_stream_t s_) {
-  SPGAN_CHECK_ARG(xyz && new_xyz && out && B > 0 && N > 0 && S > 0 && nsample > 0 && (C == 2 || C == 3));
-  const float r2 = radius * radius;
+  SPGAN_CHECK_ARG(xyz && new_xyz && out && B > 0 && N > 0 && S > 0 && nsample > 0 && (C == 2 || C == 3) && thr >= 0.f);
   dim3 grid(cdiv(S, 256), B);
-  if (C == 3) hipLaunchKernelGGL((ball_query_kernel<3>), grid, dim3(256), 0, (hipStream_t)s_, xyz, new_xyz, N, S, r2, nsample, out);
-  else hipLaunchKernelGGL((ball_query_kernel<2>), grid, dim3(256), 0, (hipStream_t)s_, xyz, new_xyz, N, S, r2, nsample, out);
+  if (C == 3) hipLaunchKernelGGL((ball_query_kernel<3>), grid, dim3(256), 0, (hipStream_t)s_, xyz, new_xyz, N, S, thr, nsample, out);
+  else hipLaunchKernelGGL((ball_query_kernel<2>), grid, dim3(256), 0, (hipStream_t)s_, xyz, new_xyz, N, S, thr, nsample, out);
   return spgan_launch_status();
 }
 

@@ -24,6 +24,7 @@ PointNet++ modules (Common/pointnet_util.py:146-320; inputs / outputs channel-ma
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -116,12 +117,21 @@ def farthest_point_sample(xyz: Tensor, npoint: int, start: Optional[Tensor] = No
     return out
 
 
+def ball_threshold(radius: float) -> float:
+    """The float32 `thr` for which `d > thr` equals the reference's `sqrdists > radius ** 2` for every float32 d: torch casts the Python
+    double radius ** 2 to the tensor's float32 (round to nearest) and compares there.  Formed from the double, never from a float32 radius."""
+    return ctypes.c_float(float(radius) ** 2).value
+
+
 def query_ball_point(radius: float, nsample: int, xyz: Tensor, new_xyz: Tensor) -> Tensor:
+    """The first `nsample` points (ascending index) the reference's mask `sqrdists > radius ** 2` leaves in, padded with the first of them;
+    an empty ball gives N in every slot (pointnet_util.py:87-107).  A point exactly on the threshold is inside.  nsample > N (where the
+    reference raises an IndexError): still nsample columns, padded the same way."""
     xyz, new_xyz = _xyz(xyz, "xyz"), _xyz(new_xyz, "new_xyz")
     B, N, C = xyz.shape
     S = new_xyz.shape[1]
     out = torch.empty((B, S, nsample), dtype=torch.int64, device=xyz.device)
-    check(_lib.load().spgan_query_ball_point(float(radius), nsample, _p(xyz), _p(new_xyz), B, N, S, C, _p(out), _s()), "query_ball_point",
+    check(_lib.load().spgan_query_ball_point(ball_threshold(radius), nsample, _p(xyz), _p(new_xyz), B, N, S, C, _p(out), _s()), "query_ball_point",
           B=B, N=N, S=S, C=C)
     return out
 

@@ -39,6 +39,8 @@ def test_argument_validation_without_gpu():
     assert lib.spgan_knn(None, 1, 16, 3, 4, 0, None, None) == -22
     assert lib.spgan_knn(1, 1, 16, 3, 40, 0, 1, None) == -22          # k > 32
     assert lib.spgan_gemm_tn_ws_bytes(0, 4, 4) == 0
+    assert lib.spgan_query_ball_point(-1.0, 1, 1, 1, 1, 1, 1, 3, 1, None) == -22          # its first argument is a threshold on d^2: >= 0
+    assert lib.spgan_query_ball_point(float("nan"), 1, 1, 1, 1, 1, 1, 3, 1, None) == -22
     with pytest.raises(RuntimeError):
         _lib.check(-22, "knn", B=1)
     # the grouped launches (round 5): count outside 1 .. SPGAN_GROUP_MAX, problems of different geometry, missing pointers
