@@ -1385,6 +1385,32 @@ int spgan_sa_scatter(const float* dY, int ld, int C, const int32_t* rowptr, cons
 int spgan_sa_rows_to_cm_slice(const float* rows, int B, int S, int C, int c0, int Ctot, float* cm, spgan_stream_t s);
 int spgan_sa_cm_slice_to_rows(const float* cm, int B, int S, int C, int c0, int Ctot, float* rows, spgan_stream_t s);
 
+/* ----------------------------------------------------------------------------------------
+ * Frechet point-cloud distance in float64 on v_mfma_f64_16x16x4_f64 (csrc/frechet.hip; Common/GAN_metrics.py:484-545).  Every matrix
+ * is square [d,d], row-major, 2 <= d <= 2048; every sum has a fixed order (no float atomics): equal inputs give equal bits.
+ * spgan_f64_gemm: C = alpha op(A) B + beta C + diag I, op(A) = A^T if trans_a (beta == 0: C is not read); C must not alias A or B.
+ * spgan_f64_reduce: out[0] = trace(A) (kind 0), |A|_F (kind 1) or sum A o B (kind 2); ws of spgan_f64_reduce_ws_bytes().
+ * spgan_fpd_moments_update: one chunk X [n,d] of float32 rows into the running state (count_before rows seen, sum2 [2,d], M2 [d,d]):
+ *   the chunk's float64 column sums and centred Gram matrix (converted and centred while staged), merged by
+ *   M2 += M2_chunk + (na nb / (na + nb)) delta delta^T.  sum2[0] is the pivot (the first row ever seen), sum2[1] the sums of
+ *   x - pivot: a large common mean cancels exactly instead of rounding every sum; mean = sum2[0] + sum2[1] / count.
+ *   count_before == 0 overwrites sum2 and M2.  The caller keeps the count.
+ * spgan_fpd_distance: out5 = [|mu1 - mu2|^2 + tr(S1 + S2 - 2 sqrt(S1 S2)), iterations of stages 0, 1, 2, tr sqrt(S1 S2)].
+ *   Stages 0 and 1: R = sqrt(S1), sqrt(S2) by the coupled Newton-Schulz iteration, stopped on the device when
+ *   |Y_new - Y|_F <= 1e-13 |Y_new|_F; stage 2: the nuclear norm of R1 R2 (= tr sqrt(S1 S2)) by the polar iteration
+ *   X <- X (1.5 I - 0.5 X^T X), stopped when sum X o (R1 R2) moves by <= 1e-14 of itself; each stage after at most
+ *   spgan_fpd_max_iterations().  Stream-ordered, no host read; ws of spgan_fpd_distance_ws_bytes(d), 256-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+int spgan_f64_gemm(const double* A, const double* B, double* C, int d, int trans_a, double alpha, double beta, double diag, spgan_stream_t s);
+size_t spgan_f64_reduce_ws_bytes(void);
+int spgan_f64_reduce(int kind, const double* A, const double* B, int d, double* out, void* ws, spgan_stream_t s);
+size_t spgan_fpd_moments_ws_bytes(int n, int d);
+int spgan_fpd_moments_update(const float* X, int n, int d, long count_before, double* sum2, double* M2, void* ws, size_t ws_bytes, spgan_stream_t s);
+int spgan_fpd_max_iterations(void);
+size_t spgan_fpd_distance_ws_bytes(int d);
+int spgan_fpd_distance(const double* mu1, const double* S1, const double* mu2, const double* S2, int d, double* out5, void* ws, size_t ws_bytes,
+                       spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ Importing the package does not touch the GPU; the shared library is loaded on fi
 absence is a hard error (there is no CPU fallback).
 """
 from . import block_tail, dataset, edge_conv, edge_max, edge_rank, edge_weight, edge_window, fixture_rng, metrics, ops, pointconv_util, pointnet_util, point_attn, gc_attn, sampling  # noqa: F401
-from . import compat, pointops                                            # noqa: F401
+from . import compat, fpd, pointops                                       # noqa: F401
 from . import pointnet2_modules, pointnet2_utils, pytorch_utils            # noqa: F401
 from .capture import CapturedBody                                          # noqa: F401
 from .losses import GradientPenalty, dis_loss, gen_loss                    # noqa: F401
@@ -29,5 +29,5 @@ __all__ = ["Generator", "Discriminator", "EdgeBlock", "AdaptivePointNorm", "get_
            "bilateral_block_l2", "bilateral_block_l3", "bilateral_block_l4", "deform_block_middle", "deform_block_tail", "deform_block_feat_middle",
            "deform_block_feat", "PointTransformerLayer", "Attention", "Self_Attn", "Self_Attn2", "DenseEdgeModule", "DenseModule1D", "Dense_Attn", "GC_attn", "DenseModule2D", "MultiDenseMLP", "Dense_Attn_2D", "get_graph_feature", "dis_loss", "gen_loss",
            "expansionPenaltyFunction", "expansionPenaltyModule", "minimum_density_sample", "gather_operation",
-           "GradientPenalty", "TrainStep", "CapturedBody", "Adam", "EMA", "StepLR", "DataParallel", "requires_grad", "ops", "fixture_rng", "sampling", "pointops", "compat",
+           "GradientPenalty", "TrainStep", "CapturedBody", "Adam", "EMA", "StepLR", "DataParallel", "requires_grad", "ops", "fixture_rng", "sampling", "pointops", "compat", "fpd",
            "pointnet2_utils", "pointnet2_modules", "pytorch_utils"]

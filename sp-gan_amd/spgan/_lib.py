@@ -433,6 +433,14 @@ SIGNATURES = {
     "spgan_sa_scatter": (I, [P, I, I, P, P, I, P, I, I, I, I, P, I, I, P]),
     "spgan_sa_rows_to_cm_slice": (I, [P, I, I, I, I, I, P, P]),
     "spgan_sa_cm_slice_to_rows": (I, [P, I, I, I, I, I, P, P]),
+    "spgan_f64_gemm": (I, [P, P, P, I, I, C.c_double, C.c_double, C.c_double, P]),
+    "spgan_f64_reduce_ws_bytes": (SZ, []),
+    "spgan_f64_reduce": (I, [I, P, P, I, P, P, P]),
+    "spgan_fpd_moments_ws_bytes": (SZ, [I, I]),
+    "spgan_fpd_moments_update": (I, [P, I, I, LG, P, P, P, SZ, P]),
+    "spgan_fpd_max_iterations": (I, []),
+    "spgan_fpd_distance_ws_bytes": (SZ, [I]),
+    "spgan_fpd_distance": (I, [P, P, P, P, I, P, P, SZ, P]),
 }
 
 _lib = None

@@ -16,10 +16,13 @@ The chunk-sum quirk.  The reference's pairwise_local_CD calls local_CD on a samp
 at once, and local_CD sums over that batch, so it returns [S, ceil(R / batch_size)] chunk sums, not an [S,R] matrix (batch_size = 1
 gives the matrix).  pairwise_local_CD here reproduces that; pairwise_dists, and with it both drivers, use the per-pair matrix.
 
-Not available: FPD needs activations from `evaluation.pointnet`, which the reference tree does not contain; compute_all_metrics on
-2-D inputs and compute_all_metrics_train(use_FPD_JSD=True) raise NotImplementedError.  "EMD" dispatches to spgan.metrics.pairwise_emd
-(the tree's auction, mean over the points of sqrt(dist)), not the reference's emd_approx of this module (300 iterations, mean of the
-squared distances over a whole chunk).
+FPD (spgan.fpd: float64 MFMA kernels) is opt-in.  The pretrained feature network `evaluation.pointnet` is not part of the reference
+tree and is not provided, so by default compute_all_metrics on 2-D inputs and compute_all_metrics_train(use_FPD_JSD=True) raise
+NotImplementedError as before.  compute_all_metrics(..., fpd=True) on 2-D feature rows runs the reference's branch (l2 distances over
+the features, FPD filled in); compute_all_metrics_train(..., model=<module>, use_FPD_JSD=True) takes the caller's network, computes its
+activations, JSD and FPD (the reference computes the activations and leaves its FPD line commented out, so its FPD stays 0).
+"EMD" dispatches to spgan.metrics.pairwise_emd (the tree's auction, mean over the points of sqrt(dist)), not the reference's emd_approx
+of this module (300 iterations, mean of the squared distances over a whole chunk).
 """
 from __future__ import annotations
 
@@ -29,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .fpd import FPD, extract_acts_with_model
 from .local_cd import pairwise_local_cd
 from .metrics import _entropy, _matrix, lgan_mmd_cov, pairwise_cd, pairwise_emd
 from .ops import _f32, _p, _s, check
@@ -36,7 +40,7 @@ from .ops import _f32, _p, _s, check
 Tensor = torch.Tensor
 
 _NO_POINTNET = ("FPD needs PointNet activations from `evaluation.pointnet` (PointNetCls), which the reference tree does not "
-                "contain; it is not available here")
+                "contain; it is not available here (pass fpd=True with feature rows, or model=<your network> with use_FPD_JSD=True)")
 
 
 def _dev(x) -> Tensor:
@@ -160,11 +164,16 @@ def _three(sample_pcs, ref_pcs, batch_size, dist_type):
     return ss, rr, sr
 
 
-def compute_all_metrics(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int = 16, dist_type: str = "CD") -> Dict[str, float]:
-    """GAN_metrics.py:796-831 -> {"JSD", "COV", "MMD", "1NN", "6NN", "FPD"} (FPD 0.0 on clouds, as there)."""
+def compute_all_metrics(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int = 16, dist_type: str = "CD", fpd: bool = False) -> Dict[str, float]:
+    """GAN_metrics.py:796-831 -> {"JSD", "COV", "MMD", "1NN", "6NN", "FPD"} (FPD 0.0 on clouds, as there).  2-D inputs are feature
+    rows: with fpd=True the reference's branch (:815-816) runs -- the distances over the features, JSD 0.0 and FPD(sample, ref);
+    without it they are refused."""
     sample_pcs, ref_pcs = _dev(sample_pcs), _dev(ref_pcs)
     if sample_pcs.dim() == 2:
-        raise NotImplementedError(_NO_POINTNET)
+        if not fpd:
+            raise NotImplementedError(_NO_POINTNET)
+        ss, rr, sr = _three(sample_pcs, ref_pcs, batch_size, dist_type)
+        return {"JSD": 0.0, "COV": COV(sr), "MMD": MMD(sr), "1NN": KNN(ss, sr, rr, 1), "6NN": KNN(ss, sr, rr, 6), "FPD": FPD(sample_pcs, ref_pcs)}
     ss, rr, sr = _three(sample_pcs, ref_pcs, batch_size, dist_type)
     return {"JSD": JSD(sample_pcs, ref_pcs, "gen", "ref", False), "COV": COV(sr), "MMD": MMD(sr), "1NN": KNN(ss, sr, rr, 1),
             "6NN": KNN(ss, sr, rr, 6), "FPD": 0.0}
@@ -172,12 +181,19 @@ def compute_all_metrics(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int = 1
 
 def compute_all_metrics_train(sample_pcs: Tensor, ref_pcs: Tensor, model=None, batch_size: int = 16, dist_type: str = "CD",
                               use_FPD_JSD: bool = False) -> Dict[str, float]:
-    """GAN_metrics.py:762-793 -> {"JSD", "COV", "MMD", "MMD_t", "1NN", "FPD"}; JSD and FPD stay 0 (use_FPD_JSD needs the model
-    activations of `evaluation.pointnet`)."""
-    if use_FPD_JSD:
+    """GAN_metrics.py:762-793 -> {"JSD", "COV", "MMD", "MMD_t", "1NN", "FPD"}; JSD and FPD stay 0 unless use_FPD_JSD, which needs
+    `model` (a module whose forward returns (_, activations)): then JSD of the clouds and FPD of the model's activations are filled
+    in (the reference computes the activations and stops there: its FPD line is commented out)."""
+    if use_FPD_JSD and model is None:
         raise NotImplementedError(_NO_POINTNET)
     ss, rr, sr = _three(sample_pcs, ref_pcs, batch_size, dist_type)
-    return {"JSD": 0, "COV": COV(sr), "MMD": MMD(sr), "MMD_t": MMD(sr.t()), "1NN": KNN(ss, sr, rr, 1), "FPD": 0}
+    fpd, jsd = 0, 0
+    if use_FPD_JSD:
+        sample_pcs, ref_pcs = _dev(sample_pcs), _dev(ref_pcs)
+        sample_buf, ref_buf = extract_acts_with_model([sample_pcs, ref_pcs], model, batch_size=batch_size)
+        fpd = FPD(sample_buf, ref_buf)
+        jsd = JSD(sample_pcs, ref_pcs, "gen", "ref", False)
+    return {"JSD": jsd, "COV": COV(sr), "MMD": MMD(sr), "MMD_t": MMD(sr.t()), "1NN": KNN(ss, sr, rr, 1), "FPD": fpd}
 
 
 __all__ = ["pairwise_dists", "pairwise_simple", "pairwise_local_CD", "COV", "MMD", "KNN", "JSD", "get_voxel_occ_dist", "voxel_counts",
