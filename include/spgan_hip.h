@@ -1411,6 +1411,65 @@ size_t spgan_fpd_distance_ws_bytes(int d);
 int spgan_fpd_distance(const double* mu1, const double* S1, const double* mu2, const double* S2, int d, double* out5, void* ws, size_t ws_bytes,
                        spgan_stream_t s);
 
+/* ----------------------------------------------------------------------------------------
+ * GAN-stabiliser and StyleGAN-style layers (csrc/gan_layers.hip; Generation/modules.py:32-390, 437-496).  fp32, no float atomics, fixed
+ * summation orders (equal inputs give equal bits; a problem gives the same bits alone and inside a group), no host read.
+ *
+ * Grouped spectral normalisation: `count` (1 .. SPGAN_SN_MAX) weights W[p] [h,w] row-major (the parameter flattened from dim 0) as one
+ * argument block; the number of launches does not depend on count (4 per power iteration + 1; 3 with n_iter == 0).
+ *   forward: n_iter times  v <- norm(W^T u), u <- norm(W v)  (u [h], v [w] updated in place), sigma = u . (W v), out = W / sigma;
+ *     rule 0: norm(x) = x / (|x| + eps) (the reference's l2normalize), rule 1: x / max(|x|, eps) (F.normalize).  n_iter == 0 leaves u, v
+ *     alone (eval mode of the hook form).  save[p] [1 + h + w] receives (sigma, u, v) of this call; ws[p] holds
+ *     spgan_sn_ws_floats(h, w) floats.  W^T u runs as 16-row chunks x 256-column blocks, W v as one wave per row, the quotient as
+ *     2048-element tiles: a [512,1024] weight spreads over 128 / 128 / 256 workgroups.
+ *   backward (u, v constant): dW = G / sigma - (<G,W> / sigma^2) u v^T from save[p]; one grouped reduction (2048-element tiles into
+ *     ws[p]), one grouped apply.  Reads W, G, save, ws; writes dW.
+ * ---------------------------------------------------------------------------------------- */
+#define SPGAN_SN_MAX 32
+typedef struct spgan_sn_args {
+  int count;
+  const float* W[SPGAN_SN_MAX]; float* u[SPGAN_SN_MAX]; float* v[SPGAN_SN_MAX]; float* out[SPGAN_SN_MAX];
+  float* save[SPGAN_SN_MAX]; float* ws[SPGAN_SN_MAX];
+  const float* G[SPGAN_SN_MAX]; float* dW[SPGAN_SN_MAX];          /* backward only */
+  int h[SPGAN_SN_MAX], w[SPGAN_SN_MAX];
+} spgan_sn_args;
+size_t spgan_sn_ws_floats(int h, int w);
+int spgan_sn_forward(const spgan_sn_args* a, int n_iter, int rule, float eps, spgan_stream_t s);
+int spgan_sn_backward(const spgan_sn_args* a, spgan_stream_t s);
+/* Minibatch stddev (modules.py:54-135): x [B,C,N], G | B, M = B/G, sample b = g*M + m belongs to statistic m; F | C new channels.
+ *   forward: one pass copies x into out [B,C+F,N] channels [0,C) and reduces sqrt(mean_g (x - mean_g)^2 + alpha) per (m, c, 1024-point
+ *     tile) into ws (spgan_mbstd_ws_floats floats); a second launch averages the records of a feature group and fills channels [C,C+F).
+ *   backward: S [M,F] = sum over g, n of dout's new channels; dx = dout[:, :C] + S (x - mean) / (G std (C/F) N). */
+size_t spgan_mbstd_ws_floats(int B, int C, int N, int G);
+int spgan_mbstd_forward(const float* x, int B, int C, int N, int G, int F, float alpha, float* out, float* ws, spgan_stream_t s);
+int spgan_mbstd_backward(const float* x, const float* dout, int B, int C, int N, int G, int F, float alpha, float* dx, float* S,
+                         spgan_stream_t s);
+/* The layer epilogue  y = gamma * IN(PN(act(x + w * noise))) + beta  on x [B,C,L], C <= SPGAN_EPILOGUE_MAX_C; every stage optional.
+ *   noise [B,L] with w [C] (both or neither);  act 0 none, 1 ReLU, 2 LeakyReLU(slope);  pn 0 none, 1 t = a * rsqrt(mean_c a^2 + pn_eps),
+ *   2 t = a / sqrt(mean_c a^2 + pn_eps);  stats 0 none, 1 per (b,c) over L, 2 per b over C*L jointly (biased variance, in_eps; C*L > 1);
+ *   gamma, beta: element (b, c) at [b*ld_gb + c] (both or neither).
+ *   rs [B,L] (pn != 0), stat [B,C,2] or [B,2] (mean, invstd; stats != 0) are written by the forward and read by the backward;
+ *   rec holds spgan_epilogue_rec_floats(B, C, L) floats of per-(b, c, 256-point tile) records (stats != 0, or backward with dgamma / dw).
+ *   forward: with statistics a column pass (rs and records), a finalising launch, an element-wise apply; pixel norm alone: the column pass
+ *     writes y; neither: the apply alone.  t is never stored.
+ *   backward: dx [B,C,L], dnoise [B,L], dw [C], dgamma / dbeta (element (b, c) at [b*ld_d + c]), each optional; grp [B,C,2] or [B,2]
+ *     scratch (stats != 0).  A reduction pass and its finalising launch (statistics or dgamma), a column pass, and a launch for dw. */
+#define SPGAN_EPILOGUE_MAX_C 1024
+typedef struct spgan_epilogue_args {
+  const float* x; const float* noise; const float* w; const float* gamma; const float* beta; int ld_gb;
+  int B, C, L, act, pn, stats;
+  float slope, pn_eps, in_eps;
+  float* rs; float* stat; float* rec;
+} spgan_epilogue_args;
+size_t spgan_epilogue_rec_floats(int B, int C, int L);
+int spgan_epilogue_forward(const spgan_epilogue_args* a, float* y, spgan_stream_t s);
+int spgan_epilogue_backward(const spgan_epilogue_args* a, const float* dy, float* dx, float* dnoise, float* dw, float* dgamma, float* dbeta,
+                            int ld_d, float* grp, spgan_stream_t s);
+/* Truncation (modules.py:312-327) on x [B,Lr,D]: out = l < max_layer ? lerp(avg, x, thr) : x, avg [D] or (avg_per_layer) [Lr,D];
+ * bwd != 0: out = x * (l < max_layer ? thr : 1), the cotangent's pass (avg not read). */
+int spgan_truncation(const float* x, const float* avg, int avg_per_layer, int B, int Lr, int D, int max_layer, float thr, int bwd, float* out,
+                     spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

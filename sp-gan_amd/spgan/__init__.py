@@ -18,6 +18,10 @@ from .modules import (bilateral_block, bilateral_block_l1, bilateral_block_l2, b
 from .modules import Attention, PointTransformerLayer, Self_Attn            # noqa: F401
 from .modules import Dense_Attn, DenseEdgeModule, DenseModule1D, get_graph_feature            # noqa: F401
 from .modules import Dense_Attn_2D, DenseModule2D, GC_attn, MultiDenseMLP, Self_Attn2                                        # noqa: F401
+from . import gan_layers                                                    # noqa: F401
+from .gan_layers import (AdaptiveInstanceNorm, LayerEpilogue, MinibatchStdDev, NoiseInjection, NoiseLayer, PixelNorm, PixelwiseNorm,   # noqa: F401
+                         SpectralNorm, StddevLayer, Truncation, WScaleLayer, l2normalize, snconv2d, snlinear, spectral_norm,
+                         spectral_norm_network)
 from .expansion_penalty import expansionPenaltyFunction, expansionPenaltyModule   # noqa: F401
 from .mds import gather_operation, minimum_density_sample                       # noqa: F401
 from .optim import EMA, Adam, StepLR, flatten_module                       # noqa: F401
@@ -30,4 +34,7 @@ __all__ = ["Generator", "Discriminator", "EdgeBlock", "AdaptivePointNorm", "get_
            "deform_block_feat", "PointTransformerLayer", "Attention", "Self_Attn", "Self_Attn2", "DenseEdgeModule", "DenseModule1D", "Dense_Attn", "GC_attn", "DenseModule2D", "MultiDenseMLP", "Dense_Attn_2D", "get_graph_feature", "dis_loss", "gen_loss",
            "expansionPenaltyFunction", "expansionPenaltyModule", "minimum_density_sample", "gather_operation",
            "GradientPenalty", "TrainStep", "CapturedBody", "Adam", "EMA", "StepLR", "DataParallel", "requires_grad", "ops", "fixture_rng", "sampling", "pointops", "compat", "fpd",
-           "pointnet2_utils", "pointnet2_modules", "pytorch_utils"]
+           "pointnet2_utils", "pointnet2_modules", "pytorch_utils",
+           "gan_layers", "SpectralNorm", "spectral_norm", "spectral_norm_network", "snconv2d", "snlinear", "l2normalize", "MinibatchStdDev",
+           "StddevLayer", "PixelNorm", "PixelwiseNorm", "NoiseLayer", "NoiseInjection", "LayerEpilogue", "AdaptiveInstanceNorm", "WScaleLayer",
+           "Truncation"]

@@ -177,6 +177,25 @@ class SaQueryArgs(C.Structure):
                 ("idx", C.c_void_p * SA_MAX_SCALES)]
 
 
+SN_MAX = 32             # SPGAN_SN_MAX: weights per grouped spectral-norm call
+EPILOGUE_MAX_C = 1024   # SPGAN_EPILOGUE_MAX_C
+
+
+class SnArgs(C.Structure):
+    """spgan_sn_args"""
+    _fields_ = [("count", C.c_int), ("W", C.c_void_p * SN_MAX), ("u", C.c_void_p * SN_MAX), ("v", C.c_void_p * SN_MAX),
+                ("out", C.c_void_p * SN_MAX), ("save", C.c_void_p * SN_MAX), ("ws", C.c_void_p * SN_MAX),
+                ("G", C.c_void_p * SN_MAX), ("dW", C.c_void_p * SN_MAX), ("h", C.c_int * SN_MAX), ("w", C.c_int * SN_MAX)]
+
+
+class EpilogueArgs(C.Structure):
+    """spgan_epilogue_args"""
+    _fields_ = [("x", C.c_void_p), ("noise", C.c_void_p), ("w", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("ld_gb", C.c_int),
+                ("B", C.c_int), ("C", C.c_int), ("L", C.c_int), ("act", C.c_int), ("pn", C.c_int), ("stats", C.c_int),
+                ("slope", C.c_float), ("pn_eps", C.c_float), ("in_eps", C.c_float),
+                ("rs", C.c_void_p), ("stat", C.c_void_p), ("rec", C.c_void_p)]
+
+
 I, F, P, SZ = C.c_int, C.c_float, C.c_void_p, C.c_size_t
 LG, GCB = C.c_long, C.POINTER(GcBranch)
 
@@ -441,6 +460,16 @@ SIGNATURES = {
     "spgan_fpd_max_iterations": (I, []),
     "spgan_fpd_distance_ws_bytes": (SZ, [I]),
     "spgan_fpd_distance": (I, [P, P, P, P, I, P, P, SZ, P]),
+    "spgan_sn_ws_floats": (SZ, [I, I]),
+    "spgan_sn_forward": (I, [C.POINTER(SnArgs), I, I, F, P]),
+    "spgan_sn_backward": (I, [C.POINTER(SnArgs), P]),
+    "spgan_mbstd_ws_floats": (SZ, [I, I, I, I]),
+    "spgan_mbstd_forward": (I, [P, I, I, I, I, I, F, P, P, P]),
+    "spgan_mbstd_backward": (I, [P, P, I, I, I, I, I, F, P, P, P]),
+    "spgan_epilogue_rec_floats": (SZ, [I, I, I]),
+    "spgan_epilogue_forward": (I, [C.POINTER(EpilogueArgs), P, P]),
+    "spgan_epilogue_backward": (I, [C.POINTER(EpilogueArgs), P, P, P, P, P, P, I, P, P]),
+    "spgan_truncation": (I, [P, P, I, I, I, I, I, F, I, P, P]),
 }
 
 _lib = None
