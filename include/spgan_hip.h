@@ -199,6 +199,16 @@ typedef struct spgan_gemm_nt_args {
   const float* ad_mean; const float* ad_var; float ad_eps, ad_slope;
   float* ad_gamma; int ad_ld_gamma, ad_gamma_row0;
 } spgan_gemm_nt_args;
+/* The kernel spgan_gemm_nt runs for this problem (0: a == NULL): the one decision (csrc/gemm_nt_plan.hpp) the launch executes and the
+ * queries below read.  None of them reads through a pointer of the block; all honour tile_hint and the SPGAN_NT_* environment switches. */
+enum { SPGAN_NT_KERNEL_K4_STREAM = 1, SPGAN_NT_KERNEL_SMALL = 2, SPGAN_NT_KERNEL_TILE = 3, SPGAN_NT_KERNEL_WIDE = 4, SPGAN_NT_KERNEL_WIDE16 = 5,
+       SPGAN_NT_KERNEL_WIDE3 = 6 };
+int spgan_gemm_nt_kernel(const spgan_gemm_nt_args* a);
+/* The whole plan as integers, for tests and tools: out[0..9] = kernel, invalid (tail.enabled with no column-owning kernel: the launch returns
+ * SPGAN_EINVAL), tile_n, owns_columns, the 128-row family's CFG, DB, FAST, operand form (0 fp32 / 1 fp16 / 2 split-bf16) and 16-bit-storage
+ * flag (meaningful for SPGAN_NT_KERNEL_TILE), the split-bf16 256-row-tile configuration 24 / 22 / 14 (SPGAN_NT_KERNEL_WIDE3, else 0). */
+#define SPGAN_NT_PLAN_FIELDS 10
+int spgan_gemm_nt_plan(const spgan_gemm_nt_args* a, int32_t* out);
 /* 1 when spgan_gemm_nt will honour y_bf16 for this problem (it runs on the 256 x 256-tile kernel with fp16 operands) */
 int spgan_gemm_nt_y16_ok(const spgan_gemm_nt_args* a);
 /* 1 when spgan_gemm_nt will run this problem on the M <= 64 kernel, i.e. when `tail.enabled` is acceptable (else the launch

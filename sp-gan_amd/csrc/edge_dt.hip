@@ -26,7 +26,7 @@
 // 361 us against this form's 356 us in the train step on one machine and was not kept.
 #include <stdlib.h>
 #include "edge_attend.hpp"
-#include "gemm_wide.hpp"
+#include "gemm_nt_plan.hpp"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -194,7 +194,7 @@ extern "C" int spgan_edge_attend_bwd_dt_selected(const float* dout, int ldo, con
   a.Y = const_cast<float*>(dout); a.ldy = k * F;   // any non-null address: the selection never reads through it
   a.M = M; a.N = k * F; a.K = F;
   a.a_mode = SPGAN_A_PLAIN; a.epi_mode = SPGAN_EPI_LINEAR; a.mfma_f16 = 0; a.tile_hint = tile_hint;
-  return spgan_nt_wide_selected(a) ? 1 : 0;
+  return nt_plan(a).kernel == NT_WIDE ? 1 : 0;
 }
 
 extern "C" int spgan_edge_attend_bwd_dt(const float* dout, int ldo, const float* WoT, int ldw, const float* h2pre, const float* sc2,

@@ -22,10 +22,12 @@
 // EdgeBlock per-edge difference gather, bias / per-shape bias / activation, per-tile column statistics
 // for the following train-mode BatchNorm, and the LeakyReLU/BatchNorm backward masks with their
 // column sums.
+#include <cstring>
 #include <type_traits>
 
 #include "common.hpp"
 #include "adain_epi.hpp"
+#include "gemm_nt_plan.hpp"
 #include "gemm_wide.hpp"
 #include "gemm_tn_wide3.hpp"
 #include "sparse_rows.hpp"
@@ -40,10 +42,10 @@ namespace {
 
 // internal operand mode: A_AFFINE_LRELU with the sparse addend (sp_val != NULL) -- its own instantiation, so the plain
 // affine kernels do not carry the addend's registers and LDS-patch code
-constexpr int A_AFFINE_SPARSE = 3;
+constexpr int A_AFFINE_SPARSE = NT_A_AFFINE_SPARSE;
 // internal operand mode: a = A*p_scale[k] + A2*p_scale2[k] + p_shift[k] (two tensors, no activation): the BatchNorm-backward operand
 // dy = p*g + q*y + r evaluated on the operand load instead of by a pass of its own (spgan_gemm_nt_args.A2)
-constexpr int A_AFFINE2 = 4;
+constexpr int A_AFFINE2 = NT_A_AFFINE2;
 
 constexpr int BM = 128;
 constexpr int BK = 32;
@@ -1055,8 +1057,6 @@ void launch_nt_cfg(const spgan_gemm_nt_args& a, hipStream_t s) {
   hipLaunchKernelGGL((gemm_nt_kernel<AMODE, EPI, CFG, DB, FAST, F16, AH>), dim3(tm8 * cdiv(a.N, BN), batch), dim3(256), lds, s, a);
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 // ------------------------------------------------------------------------------------------ gemm_nt, M <= 64
 // The per-shape linears (D's fc head, G's global_conv: M = batch size, Discriminator.py:83-95, Generator.py:119-126)
 // have no use for 128-row MFMA tiles: one workgroup would walk all of K alone (87 us for 32x512x1024).  Here a
@@ -1262,86 +1262,52 @@ __global__ __launch_bounds__(256) void gemm_nt_k4_kernel(const spgan_gemm_nt_arg
   }
 }
 
-// which problems the streaming kernel takes (nothing on the host mirrors this: neither results nor layouts depend on it)
-inline bool nt_skinny_on(const spgan_gemm_nt_args& a) {
-  return a.tile_hint != 1 && a.M > 64 && a.batch <= 1 && !a.tail.enabled && !a.pool_val && !a.sp_val && !a.A2 && !a.a_half && !a.y_bf16 && !a.y_half;
-}
-inline bool nt_k4_ok(const spgan_gemm_nt_args& a) {
-  if (!nt_skinny_on(a) || a.K > 4 || a.a_mode != SPGAN_A_PLAIN || a.N % 4 || a.N < 8 || a.N > 512) return false;
-  const int n4 = a.N / 4;
-  if (n4 & (n4 - 1)) return false;
-  if (a.ldy % 4 || !al16(a.Y)) return false;
-  if (a.stats) return false;   // column statistics stay with the MFMA epilogue: its reduction tree is part of the BatchNorm bits
-  // per-group bias rows: only where the MFMA kernel would take its whole-tile path (bias + group row added first: same bits)
-  if (a.rowbias && (a.rows_per_group <= 0 || a.rows_per_group % BM || a.M % BM || a.N % 64)) return false;
-  if (a.epi_mode == SPGAN_EPI_MASK_OUT) return !a.bias && !a.rowbias && a.ld_ref % 4 == 0 && al16(a.ref);
-  return a.epi_mode == SPGAN_EPI_LINEAR;
-}
-
+// Executes the plan (gemm_nt_plan.hpp).  The 256-row-tile kernels dispatch on the modes themselves (gemm_wide*.hip); for the kernels of this
+// file the guards only keep forms that no plan of the mode pair names from being instantiated.
 template <int AMODE, int EPI>
-int launch_nt(const spgan_gemm_nt_args& a, hipStream_t s) {
-  bool fast = (a.K % 4 == 0) && (a.lda % 4 == 0) && (a.ldw % 4 == 0) && al16(a.A) && al16(a.W);
-  if (AMODE != SPGAN_A_PLAIN) fast = fast && al16(a.p_scale) && al16(a.p_shift);
-  if (AMODE == SPGAN_A_EDGE) fast = fast && al16(a.e_bias);
-  if (AMODE == A_AFFINE_SPARSE) fast = fast && al16(a.sp_val) && al16(a.sp_arg);
-  if (AMODE == A_AFFINE2) fast = fast && al16(a.A2) && (a.lda2 % 4 == 0) && al16(a.p_scale2);
-  if constexpr (AMODE == SPGAN_A_PLAIN && (EPI == SPGAN_EPI_LINEAR || EPI == SPGAN_EPI_MASK_OUT)) {
-    if (nt_k4_ok(a)) {  // 3 coordinate columns in: the streaming kernel
-      hipLaunchKernelGGL((gemm_nt_k4_kernel<EPI>), dim3(cdiv(a.M, BM)), dim3(256), 0, s, a, a.N / 4);
-      return spgan_launch_status();
-    }
-  }
-  if constexpr (AMODE == A_AFFINE2 && EPI == SPGAN_EPI_EDGE_BNBWD) {
-    if (a.a_half) {  // bfloat16 g / fp16 y (validated in spgan_gemm_nt): the EdgeBlock's lazy BatchNorm-backward operand in 16-bit storage
-      if (a.N > 64 && a.K >= 512) launch_nt_cfg<AMODE, EPI, 0, 1, 1, 1, 1>(a, s);
-      else launch_nt_cfg<AMODE, EPI, 1, 0, 1, 1, 1>(a, s);
-      return spgan_launch_status();
-    }
-  }
-  if constexpr (AMODE == SPGAN_A_PLAIN && EPI == SPGAN_EPI_LINEAR) {
-    if (a.a_half) {  // fp16-stored A (validated in spgan_gemm_nt: fp16 mode, aligned, N > 32, M > 64, one product): the 128-row kernels only
-      if (a.N > 64 && a.K >= 512) launch_nt_cfg<AMODE, EPI, 0, 1, 1, 1, 1>(a, s);
-      else launch_nt_cfg<AMODE, EPI, 1, 0, 1, 1, 1>(a, s);
-      return spgan_launch_status();
-    }
-  }
-  if constexpr (AMODE != SPGAN_A_EDGE && AMODE != A_AFFINE2 && EPI != SPGAN_EPI_EDGE_BNBWD) {
-    if (spgan_nt_wide16_selected(a)) return spgan_launch_nt_wide16(a, s);  // fp16 operands, large aligned products: row-pipelined 256-row tiles (gemm_wide16.hip)
-    if (spgan_nt_wide_selected(a)) return spgan_launch_nt_wide(a, s);  // large aligned products: 256 x 256 tiles (gemm_wide.hip)
-    if (spgan_nt_wide3_selected(a)) return spgan_launch_nt_wide3(a, s);  // ... with split-bf16 operands: 256-row tiles (gemm_wide3.hip)
-  }
-  if constexpr (AMODE != SPGAN_A_EDGE && AMODE != A_AFFINE_SPARSE && AMODE != A_AFFINE2 && EPI != SPGAN_EPI_EDGE_BNBWD) {
-    if (a.M <= 64 && fast && !a.sp_val && a.batch <= 1 && !a.pool_val) {
-      const bool whole = a.stats != nullptr || EPI == SPGAN_EPI_BNBWD;  // column statistics: one workgroup walks all rows of its columns
-      hipLaunchKernelGGL((gemm_nt_small_kernel<AMODE, EPI>), dim3(cdiv(a.N, SC), (whole || a.M <= SR) ? 1 : cdiv(a.M, SR)), dim3(256), 0, s, a);
-      return spgan_launch_status();
-    }
-  }
-  if (a.tail.enabled) return SPGAN_EINVAL;  // only the M <= 64 kernel above finishes its columns in the launch (spgan_gemm_nt_owns_columns)
-  if constexpr (AMODE != A_AFFINE_SPARSE) {
-    if (a.mfma_f16 == 2 && fast && a.N > 32) {  // fp32 operands split into three bf16 terms: 128x64 tiles (three operand planes in LDS)
-      launch_nt_cfg<AMODE, EPI, 1, 0, 1, 2>(a, s);
-      return spgan_launch_status();
-    }
-    if (a.mfma_f16 == 1 && fast && a.N > 32) {  // fp16 operands (fp32 accumulate): same tiling rules
-      if (a.N > 64 && a.K >= 512) launch_nt_cfg<AMODE, EPI, 0, 1, 1, 1>(a, s);
-      else launch_nt_cfg<AMODE, EPI, 1, 0, 1, 1>(a, s);
-      return spgan_launch_status();
-    }
-  }
-  if (a.N > 64 && a.K >= 512) {  // long K: 128x128 tiles, double-buffered LDS, one barrier per k-tile
-    if (fast) launch_nt_cfg<AMODE, EPI, 0, 1, 1>(a, s);
-    else launch_nt_cfg<AMODE, EPI, 0, 1, 0>(a, s);
-  } else if (a.N > 32) {
-    // short K: 128x64 tiles.  With 2-8 k-tiles per workgroup the fixed load/epilogue latency dominates; the narrower tile
-    // doubles the workgroups (2048 instead of 1024 at M=65536, N=256: finer quantisation over the 256 CUs, 5 resident per
-    // CU instead of 3) -- measured 15-30 % faster than 128x128 on every N <= 1280, K <= 256 shape of the step.
-    if (fast) launch_nt_cfg<AMODE, EPI, 1, 0, 1>(a, s);
-    else launch_nt_cfg<AMODE, EPI, 1, 0, 0>(a, s);
+int launch_nt(const spgan_gemm_nt_args& a, const spgan_nt_plan& pl, hipStream_t s) {
+  if (pl.invalid) return SPGAN_EINVAL;
+  if (pl.kernel == NT_WIDE16) return spgan_launch_nt_wide16(a, s);
+  if (pl.kernel == NT_WIDE) return spgan_launch_nt_wide(a, s);
+  if (pl.kernel == NT_WIDE3) return spgan_launch_nt_wide3(a, pl.wide3_cfg, s);
+  if constexpr (EPI == SPGAN_EPI_ADAIN) {
+    launch_nt_cfg<AMODE, EPI, 0, 1, 1>(a, s);   // the epilogue's one 128-row form
+    return spgan_launch_status();
   } else {
-    launch_nt_cfg<AMODE, EPI, 2, 0, 0>(a, s);
+    if constexpr (AMODE == SPGAN_A_PLAIN && (EPI == SPGAN_EPI_LINEAR || EPI == SPGAN_EPI_MASK_OUT)) {
+      if (pl.kernel == NT_K4_STREAM) {
+        hipLaunchKernelGGL((gemm_nt_k4_kernel<EPI>), dim3(cdiv(a.M, BM)), dim3(256), 0, s, a, a.N / 4);
+        return spgan_launch_status();
+      }
+    }
+    if constexpr ((AMODE == SPGAN_A_PLAIN || AMODE == SPGAN_A_AFFINE_LRELU) && EPI != SPGAN_EPI_EDGE_BNBWD) {
+      if (pl.kernel == NT_SMALL) {
+        const bool whole = a.stats != nullptr || EPI == SPGAN_EPI_BNBWD;  // column statistics: one workgroup walks all rows of its columns
+        hipLaunchKernelGGL((gemm_nt_small_kernel<AMODE, EPI>), dim3(cdiv(a.N, SC), (whole || a.M <= SR) ? 1 : cdiv(a.M, SR)), dim3(256), 0, s, a);
+        return spgan_launch_status();
+      }
+    }
+    if constexpr ((AMODE == A_AFFINE2 && EPI == SPGAN_EPI_EDGE_BNBWD) || (AMODE == SPGAN_A_PLAIN && EPI == SPGAN_EPI_LINEAR)) {
+      if (pl.store16) {
+        pl.cfg == 0 ? launch_nt_cfg<AMODE, EPI, 0, 1, 1, 1, 1>(a, s) : launch_nt_cfg<AMODE, EPI, 1, 0, 1, 1, 1>(a, s);
+        return spgan_launch_status();
+      }
+    }
+    if constexpr (AMODE != A_AFFINE_SPARSE) {
+      if (pl.operand == 2) {
+        launch_nt_cfg<AMODE, EPI, 1, 0, 1, 2>(a, s);
+        return spgan_launch_status();
+      }
+      if (pl.operand == 1) {
+        pl.cfg == 0 ? launch_nt_cfg<AMODE, EPI, 0, 1, 1, 1>(a, s) : launch_nt_cfg<AMODE, EPI, 1, 0, 1, 1>(a, s);
+        return spgan_launch_status();
+      }
+    }
+    if (pl.cfg == 0) pl.tile_fast ? launch_nt_cfg<AMODE, EPI, 0, 1, 1>(a, s) : launch_nt_cfg<AMODE, EPI, 0, 1, 0>(a, s);
+    else if (pl.cfg == 1) pl.tile_fast ? launch_nt_cfg<AMODE, EPI, 1, 0, 1>(a, s) : launch_nt_cfg<AMODE, EPI, 1, 0, 0>(a, s);
+    else launch_nt_cfg<AMODE, EPI, 2, 0, 0>(a, s);
+    return spgan_launch_status();
   }
-  return spgan_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------ gemm_tn
@@ -2090,46 +2056,32 @@ int launch_tn(const spgan_gemm_tn_args& a, hipStream_t s) {
 
 }  // namespace
 
-// N-tile width launch_nt picks for this problem (must mirror launch_nt)
-static int nt_tile_n(const spgan_gemm_nt_args& a) {
-  if (a.a_mode != SPGAN_A_EDGE && !a.A2 && a.epi_mode != SPGAN_EPI_EDGE_BNBWD && spgan_nt_wide16_selected(a)) return spgan_nt_wide16_tile_n(a);
-  if (spgan_nt_wide_selected(a)) return 256;
-  if (a.a_mode != SPGAN_A_EDGE && !a.A2 && a.epi_mode != SPGAN_EPI_EDGE_BNBWD && spgan_nt_wide3_selected(a)) return spgan_nt_wide3_tile_n(a);
-  const bool fast = (a.K % 4 == 0) && (a.lda % 4 == 0) && (a.ldw % 4 == 0) && al16(a.A) && al16(a.W);
-  if (a.mfma_f16 == 2 && fast && a.N > 32 && !a.sp_val) return 64;
-  if (a.mfma_f16 == 1 && fast && a.N > 32 && !a.sp_val) return (a.N > 64 && a.K >= 512) ? 128 : 64;
-  if (a.N > 64 && a.K >= 512) return 128;
-  return a.N > 32 ? 64 : 32;
+extern "C" int spgan_gemm_nt_kernel(const spgan_gemm_nt_args* a) { return a ? nt_plan(*a).kernel : 0; }
+
+extern "C" int spgan_gemm_nt_plan(const spgan_gemm_nt_args* a, int32_t* out) {
+  SPGAN_CHECK_ARG(a && out);
+  const spgan_nt_plan p = nt_plan(*a);
+  memcpy(out, &p, SPGAN_NT_PLAN_FIELDS * sizeof(int32_t));   // the struct begins with them
+  return SPGAN_OK;
 }
 
-extern "C" int spgan_gemm_nt_col_blocks(const spgan_gemm_nt_args* a) {
-  if (!a || a->N <= 0) return 0;
-  return cdiv(a->N, nt_tile_n(*a));
-}
+extern "C" int spgan_gemm_nt_col_blocks(const spgan_gemm_nt_args* a) { return (a && a->N > 0) ? cdiv(a->N, nt_plan(*a).tile_n) : 0; }
 
-extern "C" int spgan_gemm_nt_owns_columns(const spgan_gemm_nt_args* a) {
-  // mirrors launch_nt: the M <= 64 kernel (one workgroup walks all rows of its columns) takes aligned, unbatched problems
-  if (!a || a->M <= 0 || a->M > 64 || a->sp_val || a->batch > 1 || a->pool_val || a->A2) return 0;
-  if (a->a_mode == SPGAN_A_EDGE || a->epi_mode == SPGAN_EPI_EDGE_BNBWD) return 0;
-  bool fast = (a->K % 4 == 0) && (a->lda % 4 == 0) && (a->ldw % 4 == 0) && al16(a->A) && al16(a->W);
-  if (a->a_mode != SPGAN_A_PLAIN) fast = fast && al16(a->p_scale) && al16(a->p_shift);
-  return fast ? 1 : 0;
-}
+extern "C" int spgan_gemm_nt_owns_columns(const spgan_gemm_nt_args* a) { return (a && a->M > 0 && nt_plan(*a).owns_columns) ? 1 : 0; }
 
 // y_bf16 / y_half are honoured by the fp16-operand kernels' LINEAR epilogues (128-row and 256 x 256): everything fp16 mode sends there
-extern "C" int spgan_gemm_nt_y16_ok(const spgan_gemm_nt_args* a) {
-  if (!a || a->mfma_f16 != 1 || a->epi_mode != SPGAN_EPI_LINEAR || a->act != SPGAN_ACT_NONE || a->batch > 1 || a->M <= 64 || a->N <= 32) return 0;
-  if (a->sp_val) return 0;   // the sparse-addend kernels have no fp16 form
-  bool fast = (a->K % 4 == 0) && (a->lda % 4 == 0) && (a->ldw % 4 == 0) && al16(a->A) && al16(a->W);
-  if (a->a_mode != SPGAN_A_PLAIN) fast = fast && al16(a->p_scale) && al16(a->p_shift);
-  if (a->a_mode == SPGAN_A_EDGE) fast = fast && al16(a->e_bias);
-  if (a->A2) fast = fast && al16(a->A2) && (a->lda2 % 4 == 0) && al16(a->p_scale2);
-  return fast ? 1 : 0;
+// (the sparse-addend kernels have no fp16 form)
+static bool nt_y16_ok(const spgan_gemm_nt_args& a, const spgan_nt_plan& pl) {
+  return a.mfma_f16 == 1 && a.epi_mode == SPGAN_EPI_LINEAR && a.act == SPGAN_ACT_NONE && a.batch <= 1 && a.M > 64 && a.N > 32 && !a.sp_val && pl.fast;
 }
+extern "C" int spgan_gemm_nt_y16_ok(const spgan_gemm_nt_args* a) { return (a && nt_y16_ok(*a, nt_plan(*a))) ? 1 : 0; }
+
+extern "C" int spgan_gemm_nt_uses_w_image(const spgan_gemm_nt_args* a) { return (a && nt_plan(*a).kernel == NT_WIDE3) ? 1 : 0; }
 
 extern "C" int spgan_gemm_nt(const spgan_gemm_nt_args* a, spgan_stream_t s_) {
   hipStream_t s = (hipStream_t)s_;
   SPGAN_CHECK_ARG(a && a->A && a->W && a->M > 0 && a->N > 0 && a->K > 0);
+  const spgan_nt_plan pl = nt_plan(*a);   // the kernel this block runs (reads no memory): the checks below ask it too
   SPGAN_CHECK_ARG(a->Y || (a->pool_val && a->epi_mode == SPGAN_EPI_LINEAR));
   if (a->pool_val) SPGAN_CHECK_ARG(a->pool_arg && (a->epi_mode == SPGAN_EPI_LINEAR || a->epi_mode == SPGAN_EPI_ADAIN) && a->M > 64);
   SPGAN_CHECK_ARG(a->lda >= a->K && a->ldw >= a->K && a->ldy >= (a->epi_mode == SPGAN_EPI_ADAIN ? a->N / 2 : a->N));
@@ -2147,7 +2099,7 @@ extern "C" int spgan_gemm_nt(const spgan_gemm_nt_args* a, spgan_stream_t s_) {
     SPGAN_CHECK_ARG(a->a_mode == SPGAN_A_PLAIN && a->epi_mode == SPGAN_EPI_LINEAR && a->Y && !a->stats && !a->rowbias && !a->pool_val &&
                     a->batch <= 65535 && a->batch_stride_a >= 0 && a->batch_stride_w >= 0 && a->batch_stride_y > 0);
   if (a->gout_add)   // the stored tile gout_add + gout_scale * g: an epilogue of the split-bf16 256-row-tile kernel only (its one caller's route)
-    SPGAN_CHECK_ARG(a->epi_mode == SPGAN_EPI_BNBWD && a->gout_scale && a->ld_gout_add >= a->N && a->Y && spgan_nt_wide3_selected(*a) &&
+    SPGAN_CHECK_ARG(a->epi_mode == SPGAN_EPI_BNBWD && a->gout_scale && a->ld_gout_add >= a->N && a->Y && pl.kernel == NT_WIDE3 &&
                     (uint64_t)a->M * (uint64_t)a->ld_gout_add < (1ull << 32));
   if (a->tail.enabled) {  // finished in the launch only where one workgroup owns its columns: the M <= 64 kernel
     const spgan_coltail& f = a->tail;
@@ -2162,30 +2114,28 @@ extern "C" int spgan_gemm_nt(const spgan_gemm_nt_args* a, spgan_stream_t s_) {
     if (a->a_half && !a->A2) SPGAN_CHECK_ARG(a->a_mode == SPGAN_A_PLAIN && a->epi_mode == SPGAN_EPI_LINEAR);   // fp16 A of a plain linear product
     if (a->a_half && a->A2)   // bfloat16 A + fp16 A2: the EdgeBlock's lazy BatchNorm-backward operand into the edge BatchNorm-backward epilogue
       SPGAN_CHECK_ARG(a->epi_mode == SPGAN_EPI_EDGE_BNBWD && a->lda2 % 4 == 0 && al16(a->A2) && al16(a->p_scale) && al16(a->p_shift) && al16(a->p_scale2));
-    if (a->y_bf16 || a->y_half) SPGAN_CHECK_ARG(a->Y && !(a->y_bf16 && a->y_half) && a->act == SPGAN_ACT_NONE && spgan_gemm_nt_y16_ok(a));
+    if (a->y_bf16 || a->y_half) SPGAN_CHECK_ARG(a->Y && !(a->y_bf16 && a->y_half) && a->act == SPGAN_ACT_NONE && nt_y16_ok(*a, pl));
   }
   switch (a->epi_mode) {
     case SPGAN_EPI_LINEAR:
-      if (a->a_mode == SPGAN_A_PLAIN) return launch_nt<SPGAN_A_PLAIN, SPGAN_EPI_LINEAR>(*a, s);
-      if (a->A2) return launch_nt<A_AFFINE2, SPGAN_EPI_LINEAR>(*a, s);
-      if (a->a_mode == SPGAN_A_AFFINE_LRELU)
-        return a->sp_val ? launch_nt<A_AFFINE_SPARSE, SPGAN_EPI_LINEAR>(*a, s) : launch_nt<SPGAN_A_AFFINE_LRELU, SPGAN_EPI_LINEAR>(*a, s);
-      if (a->a_mode == SPGAN_A_EDGE) return launch_nt<SPGAN_A_EDGE, SPGAN_EPI_LINEAR>(*a, s);
+      if (a->a_mode == SPGAN_A_PLAIN) return launch_nt<SPGAN_A_PLAIN, SPGAN_EPI_LINEAR>(*a, pl, s);
+      if (a->A2) return launch_nt<A_AFFINE2, SPGAN_EPI_LINEAR>(*a, pl, s);
+      if (a->a_mode == SPGAN_A_AFFINE_LRELU) return a->sp_val ? launch_nt<A_AFFINE_SPARSE, SPGAN_EPI_LINEAR>(*a, pl, s) : launch_nt<SPGAN_A_AFFINE_LRELU, SPGAN_EPI_LINEAR>(*a, pl, s);
+      if (a->a_mode == SPGAN_A_EDGE) return launch_nt<SPGAN_A_EDGE, SPGAN_EPI_LINEAR>(*a, pl, s);
       return SPGAN_EINVAL;
     case SPGAN_EPI_MASK_OUT:
       SPGAN_CHECK_ARG(a->a_mode == SPGAN_A_PLAIN && a->ref && a->ld_ref >= a->N);
-      return launch_nt<SPGAN_A_PLAIN, SPGAN_EPI_MASK_OUT>(*a, s);
+      return launch_nt<SPGAN_A_PLAIN, SPGAN_EPI_MASK_OUT>(*a, pl, s);
     case SPGAN_EPI_BNBWD:
       SPGAN_CHECK_ARG(a->a_mode != SPGAN_A_EDGE && a->ref && a->ld_ref >= a->N && a->b_scale && a->b_shift && a->b_mean && a->b_invstd);
-      if (a->A2) return launch_nt<A_AFFINE2, SPGAN_EPI_BNBWD>(*a, s);
-      if (a->a_mode == SPGAN_A_AFFINE_LRELU)
-        return a->sp_val ? launch_nt<A_AFFINE_SPARSE, SPGAN_EPI_BNBWD>(*a, s) : launch_nt<SPGAN_A_AFFINE_LRELU, SPGAN_EPI_BNBWD>(*a, s);
-      return launch_nt<SPGAN_A_PLAIN, SPGAN_EPI_BNBWD>(*a, s);
+      if (a->A2) return launch_nt<A_AFFINE2, SPGAN_EPI_BNBWD>(*a, pl, s);
+      if (a->a_mode == SPGAN_A_AFFINE_LRELU) return a->sp_val ? launch_nt<A_AFFINE_SPARSE, SPGAN_EPI_BNBWD>(*a, pl, s) : launch_nt<SPGAN_A_AFFINE_LRELU, SPGAN_EPI_BNBWD>(*a, pl, s);
+      return launch_nt<SPGAN_A_PLAIN, SPGAN_EPI_BNBWD>(*a, pl, s);
     case SPGAN_EPI_EDGE_BNBWD:
       SPGAN_CHECK_ARG((a->a_mode == SPGAN_A_PLAIN || a->A2) && a->ref && a->ld_ref >= a->N && a->b_scale && a->b_shift && a->b_mean && a->b_invstd &&
                       a->e_idx && a->e_k > 0 && a->e_bias2);
-      if (a->A2) return launch_nt<A_AFFINE2, SPGAN_EPI_EDGE_BNBWD>(*a, s);
-      return launch_nt<SPGAN_A_PLAIN, SPGAN_EPI_EDGE_BNBWD>(*a, s);
+      if (a->A2) return launch_nt<A_AFFINE2, SPGAN_EPI_EDGE_BNBWD>(*a, pl, s);
+      return launch_nt<SPGAN_A_PLAIN, SPGAN_EPI_EDGE_BNBWD>(*a, pl, s);
     case SPGAN_EPI_ADAIN: {
       // the style GEMM of an AdaptivePointNorm layer with the normalisation in its epilogue (spgan_hip.h); the kernel is chosen as for the
       // plain product of the same sizes (256 x 256 tiles or the 128-row kernel), whose k-order per output element both share
@@ -2197,9 +2147,7 @@ extern "C" int spgan_gemm_nt(const spgan_gemm_nt_args* a, spgan_stream_t s_) {
       SPGAN_CHECK_ARG((uint64_t)a->M * (uint64_t)a->ldy < (1ull << 32) && (uint64_t)a->ad_rows * (uint64_t)a->ad_ldx < (1ull << 32));
       if (a->ad_gamma) SPGAN_CHECK_ARG(a->ad_ld_gamma >= Cn && a->ad_gamma_row0 >= 0 && a->ad_gamma_row0 < a->M && (uint64_t)a->M * (uint64_t)a->ad_ld_gamma < (1ull << 32));
       if (a->pool_val) SPGAN_CHECK_ARG(a->ad_rows % BM == 0);   // a record tile never straddles two shapes
-      if (spgan_nt_wide_selected(*a)) return spgan_launch_nt_wide(*a, s);
-      launch_nt_cfg<SPGAN_A_PLAIN, SPGAN_EPI_ADAIN, 0, 1, 1>(*a, s);
-      return spgan_launch_status();
+      return launch_nt<SPGAN_A_PLAIN, SPGAN_EPI_ADAIN>(*a, pl, s);
     }
     default:
       return SPGAN_EINVAL;

@@ -15,7 +15,7 @@
 // prologue, statistics + pooling epilogue, output not stored) 327 -> 300 us = 73 % of the fp32 MFMA peak.
 //
 // Only straight-line code: shapes that do not tile exactly, the split-bf16 operand mode, the per-edge prologue/epilogue and the
-// in-launch fan-in stay with gemm.hip (launch_nt falls through).  fp16 operands (mfma_f16 == 1) are served here: D.fc2.0 114 -> 99 us.
+// in-launch fan-in stay with gemm.hip (spgan_nt_wide_eligible, gemm_nt_plan.hpp).  fp16 operands (mfma_f16 == 1) are served here: D.fc2.0 114 -> 99 us.
 #include <type_traits>
 #include "gemm_wide.hpp"
 #include "gemm_wide_epi.hpp"
@@ -231,50 +231,7 @@ int launch_epi(const spgan_gemm_nt_args& a, hipStream_t s) {
   return SPGAN_EINVAL;
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
-
-bool spgan_nt_wide_eligible(const spgan_gemm_nt_args& a) {
-  if (a.M < WM || a.M % WM || a.N % WN || a.K % WK || a.K < WK) return false;
-  if ((a.mfma_f16 != 0 && a.mfma_f16 != 1) || a.tail.enabled || a.batch > 1 || a.A2) return false;  // fp32 or fp16 operands (not the split-bf16 mode)
-  if (a.mfma_f16 == 1 && a.sp_val) return false;                                              // the sparse addend is an fp32-operand path (gemm.hip: same rule)
-  if (a.a_mode == SPGAN_A_EDGE || a.epi_mode == SPGAN_EPI_EDGE_BNBWD) return false;
-  if (a.lda % 4 || a.ldw % 4 || !al16(a.A) || !al16(a.W)) return false;
-  if (a.a_mode != SPGAN_A_PLAIN && (!al16(a.p_scale) || !al16(a.p_shift))) return false;
-  if (a.p_group_rows > 0 && a.p_group_rows % WM) return false;
-  if (a.sp_val) {
-    if (a.a_mode != SPGAN_A_AFFINE_LRELU || a.sp_rows % WM || !al16(a.sp_val) || !al16(a.sp_arg)) return false;
-  }
-  if (a.epi_mode == SPGAN_EPI_ADAIN) return a.a_mode == SPGAN_A_PLAIN && a.mfma_f16 == 0 && !a.rowbias && !a.stats;   // fp32 operands only
-  if (a.epi_mode == SPGAN_EPI_LINEAR) {
-    if (a.rowbias && a.rows_per_group != 1 && a.rows_per_group % WM) return false;
-    if (!a.Y && !a.stats && !a.pool_val) return false;
-  } else {
-    if (a.epi_mode == SPGAN_EPI_MASK_OUT && a.a_mode != SPGAN_A_PLAIN) return false;
-    if (a.epi_mode == SPGAN_EPI_BNBWD && a.rowbias && a.rows_per_group != 1) return false;
-    if (a.epi_mode == SPGAN_EPI_MASK_OUT && (a.bias || a.rowbias)) return false;
-  }
-  return true;
-}
-
-// Measured inside the train step (tools/mfma_shapes.py, MI355X): one workgroup per CU means a launch whose tiles make a single round
-// runs its load / MFMA / epilogue phases in lockstep on all CUs -- with a heavy epilogue (the BatchNorm-backward one reads and writes
-// [M,N]) that costs what the leaner main loop gains (65536 x 256 x 256: 103 -> 107 us), and k-loops of two tiles are all ramp
-// (K = 64: 40 -> 45 us).  Wins: 65536 x 1024 x 256 + statistics/pooling 327 -> 300 us, 65536 x 256 x 128: 57 -> 54, 65536 x 1280 x 128: 224 -> 214.
-bool spgan_nt_wide_pays(const spgan_gemm_nt_args& a) {
-  // decided from the rows of ONE group: a grouped launch (several passes of a layer as one product) must run the kernel its passes
-  // would run as separate calls -- the two kernels sum in different orders, and the grouped form is specified as bit-identical
-  const long tiles = (long)((a.p_group_rows > 0 ? a.p_group_rows : a.M) / WM) * (a.N / WN);
-  if (tiles < 256 || a.K < 128) return false;
-  return a.epi_mode == SPGAN_EPI_LINEAR || a.epi_mode == SPGAN_EPI_ADAIN || tiles >= 512;   // (ADAIN: the kernel its plain style GEMM would run)
-}
-
-bool spgan_nt_wide_selected(const spgan_gemm_nt_args& a) {
-  static const bool off = getenv("SPGAN_NT_WIDE") && atoi(getenv("SPGAN_NT_WIDE")) == 0;
-  if (off || a.tile_hint == 1 || !spgan_nt_wide_eligible(a)) return false;
-  return a.tile_hint == 2 || spgan_nt_wide_pays(a);
-}
 
 int spgan_launch_nt_wide(const spgan_gemm_nt_args& a, hipStream_t s) {
   if (a.a_mode == SPGAN_A_PLAIN) return launch_epi<SPGAN_A_PLAIN>(a, s);

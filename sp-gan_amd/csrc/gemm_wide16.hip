@@ -264,40 +264,7 @@ int launch_epi(const spgan_gemm_nt_args& a, hipStream_t s) {
   return SPGAN_EINVAL;
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
-
-bool spgan_nt_wide16_eligible(const spgan_gemm_nt_args& a) {
-  if (a.mfma_f16 != 1) return false;
-  if (a.M < 256 || a.M % 256 || a.N % 256 || a.K % (2 * HK)) return false;
-  if (a.tail.enabled || a.batch > 1 || a.A2 || a.a_half || a.sp_val) return false;
-  if (a.a_mode == SPGAN_A_EDGE || a.epi_mode == SPGAN_EPI_EDGE_BNBWD) return false;
-  if (a.lda % 4 || a.ldw % 4 || !al16(a.A) || !al16(a.W)) return false;
-  if (a.a_mode != SPGAN_A_PLAIN && (!al16(a.p_scale) || !al16(a.p_shift) || !(a.p_slope >= 0.f && a.p_slope <= 1.f))) return false;
-  if (a.p_group_rows > 0 && a.p_group_rows % 256) return false;
-  if (a.epi_mode == SPGAN_EPI_LINEAR) {
-    if (a.rowbias && a.rows_per_group != 1 && a.rows_per_group % 256) return false;
-    if (!a.Y && !a.stats && !a.pool_val) return false;
-  } else {
-    if (a.y_bf16 || a.y_half) return false;
-    if (a.epi_mode == SPGAN_EPI_MASK_OUT && a.a_mode != SPGAN_A_PLAIN) return false;
-    if (a.epi_mode == SPGAN_EPI_BNBWD && a.rowbias && a.rows_per_group != 1) return false;
-    if (a.epi_mode == SPGAN_EPI_MASK_OUT && (a.bias || a.rowbias)) return false;
-  }
-  return true;
-}
-
-// 256 x 256 tiles only: the 256 x 128 form (eight A slots per thread) spills and measured 2-3 x slower (profiles/r06_nt16_bench.txt)
-int spgan_nt_wide16_tile_n(const spgan_gemm_nt_args&) { return 256; }
-
-bool spgan_nt_wide16_selected(const spgan_gemm_nt_args& a) {
-  static const bool off = getenv("SPGAN_NT_WIDE16") && atoi(getenv("SPGAN_NT_WIDE16")) == 0;
-  if (off || a.tile_hint == 1 || !spgan_nt_wide16_eligible(a)) return false;
-  if (a.tile_hint == 2) return true;
-  // tiles of ONE group (as spgan_nt_wide_pays): a grouped launch must pick the kernel, and so the summation order, of its separate passes
-  return (long)((a.p_group_rows > 0 ? a.p_group_rows : a.M) / 256) * (a.N / 256) >= 256 && a.K >= 128;   // the tiles fill the chip, a k-loop worth its ramp
-}
 
 int spgan_launch_nt_wide16(const spgan_gemm_nt_args& a, hipStream_t s) {
   if (a.a_mode == SPGAN_A_PLAIN) return launch_epi<SPGAN_A_PLAIN>(a, s);

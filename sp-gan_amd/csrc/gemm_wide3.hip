@@ -307,11 +307,11 @@ int launch_cfg(const spgan_gemm_nt_args& a, hipStream_t s) {
 }
 
 template <int AMODE, int EPI>
-int launch(const spgan_gemm_nt_args& a, hipStream_t s) {
+int launch(const spgan_gemm_nt_args& a, int config, hipStream_t s) {
   if constexpr (AMODE == SPGAN_WIDE_A_SPARSE) {
     return launch_cfg<AMODE, EPI, 2, 4, 0>(a, s);   // the config rule's only form for the sparse addend
   } else {
-    switch (spgan_nt_wide3_config(a)) {
+    switch (config) {
       case 24: return a.w_image ? launch_cfg<AMODE, EPI, 2, 4, 1>(a, s) : launch_cfg<AMODE, EPI, 2, 4, 0>(a, s);
       case 14: return launch_cfg<AMODE, EPI, 1, 4, 1>(a, s);   // with the image only (config rule)
       default: return a.w_image ? launch_cfg<AMODE, EPI, 2, 2, 1>(a, s) : launch_cfg<AMODE, EPI, 2, 2, 0>(a, s);
@@ -320,21 +320,19 @@ int launch(const spgan_gemm_nt_args& a, hipStream_t s) {
 }
 
 template <int AMODE>
-int launch_epi(const spgan_gemm_nt_args& a, hipStream_t s) {
+int launch_epi(const spgan_gemm_nt_args& a, int config, hipStream_t s) {
   switch (a.epi_mode) {
-    case SPGAN_EPI_LINEAR: return launch<AMODE, SPGAN_EPI_LINEAR>(a, s);
-    case SPGAN_EPI_MASK_OUT: return AMODE == SPGAN_A_PLAIN ? launch<SPGAN_A_PLAIN, SPGAN_EPI_MASK_OUT>(a, s) : SPGAN_EINVAL;
+    case SPGAN_EPI_LINEAR: return launch<AMODE, SPGAN_EPI_LINEAR>(a, config, s);
+    case SPGAN_EPI_MASK_OUT: return AMODE == SPGAN_A_PLAIN ? launch<SPGAN_A_PLAIN, SPGAN_EPI_MASK_OUT>(a, config, s) : SPGAN_EINVAL;
     case SPGAN_EPI_BNBWD:
       if (a.gout_add) {   // stored tile gout_add + gout_scale * g: the activation operand only (eligibility rule)
-        if constexpr (AMODE == SPGAN_A_AFFINE_LRELU) return launch<AMODE, SPGAN_WIDE_EPI_BNBWD_GOUT>(a, s);
+        if constexpr (AMODE == SPGAN_A_AFFINE_LRELU) return launch<AMODE, SPGAN_WIDE_EPI_BNBWD_GOUT>(a, config, s);
         return SPGAN_EINVAL;
       }
-      return launch<AMODE, SPGAN_EPI_BNBWD>(a, s);
+      return launch<AMODE, SPGAN_EPI_BNBWD>(a, config, s);
   }
   return SPGAN_EINVAL;
 }
-
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 }  // namespace
 
@@ -361,63 +359,8 @@ extern "C" int spgan_split_bf16x3_image(const float* W, int ldw, int N, int K, v
   return spgan_launch_status();
 }
 
-extern "C" int spgan_gemm_nt_uses_w_image(const spgan_gemm_nt_args* a) {
-  if (!a || a->a_mode == SPGAN_A_EDGE || a->A2 || a->epi_mode == SPGAN_EPI_EDGE_BNBWD) return 0;
-  return spgan_nt_wide3_selected(*a) ? 1 : 0;
-}
-
-bool spgan_nt_wide3_eligible(const spgan_gemm_nt_args& a) {
-  if (a.mfma_f16 != 2) return false;
-  if (a.M < 256 || a.M % 256 || a.N % 128 || a.K % (2 * XK)) return false;
-  if (a.tail.enabled || a.batch > 1 || a.A2 || a.a_half || a.y_bf16 || a.y_half) return false;
-  if (a.a_mode == SPGAN_A_EDGE || a.epi_mode == SPGAN_EPI_EDGE_BNBWD) return false;
-  if (a.lda % 4 || a.ldw % 4 || !al16(a.A) || !al16(a.W) || !al16(a.w_image)) return false;
-  if (a.a_mode != SPGAN_A_PLAIN && (!al16(a.p_scale) || !al16(a.p_shift) || !(a.p_slope >= 0.f && a.p_slope <= 1.f))) return false;
-  if (a.p_group_rows > 0 && a.p_group_rows % 256) return false;
-  if (a.sp_val) {
-    if (a.a_mode != SPGAN_A_AFFINE_LRELU || a.sp_rows % 256 || a.N % 256 || !al16(a.sp_val) || !al16(a.sp_arg)) return false;
-  }
-  if (a.epi_mode == SPGAN_EPI_LINEAR) {
-    if (a.rowbias && a.rows_per_group != 1 && a.rows_per_group % 256) return false;
-    if (!a.Y && !a.stats && !a.pool_val) return false;
-  } else {
-    if (a.epi_mode == SPGAN_EPI_MASK_OUT && a.a_mode != SPGAN_A_PLAIN) return false;
-    if (a.epi_mode == SPGAN_EPI_BNBWD && a.rowbias && a.rows_per_group != 1) return false;
-    if (a.epi_mode == SPGAN_EPI_MASK_OUT && (a.bias || a.rowbias)) return false;
-  }
-  if (a.gout_add && (a.epi_mode != SPGAN_EPI_BNBWD || a.a_mode != SPGAN_A_AFFINE_LRELU || a.sp_val)) return false;
-  return true;
-}
-
-// Tile configuration (WGM*10 + WGN) of an eligible problem, from measurements on MI355X (tools/nt3_bench.py, profiles/r06_nt3_*):
-//   N % 256 != 0 -> 256 x 128 tiles (22).  Short K (<= 128): two workgroups per CU pay (one's ramp and epilogue under the other's MFMAs; the k-loop
-//   is 4-8 tiles long): 128 x 256 (14) with W's pre-split image, 256 x 128 (22) without (the B rows are then split in the workgroup, which a
-//   128-row tile would do twice as often).  Longer K: 256 x 256 tiles (24) when they fill the chip at least once (decided from the rows of ONE
-//   group, as spgan_nt_wide_pays does: a grouped launch runs the kernel its passes would run alone), else the two-workgroup forms.
-//   The sparse addend keeps to (24) without image: its extra registers spill in the other forms.
-int spgan_nt_wide3_config(const spgan_gemm_nt_args& a) {
-  static const int force = getenv("SPGAN_NT3_CFG") ? atoi(getenv("SPGAN_NT3_CFG")) : 0;   // A/B measurements: 24 / 22 / 14
-  if (a.N % 256) return 22;
-  if (a.sp_val) return 24;
-  if (force == 22 || force == 24 || (force == 14 && a.w_image)) return force;
-  const long tiles = (long)((a.p_group_rows > 0 ? a.p_group_rows : a.M) / 256) * (a.N / 256);
-  if (a.K <= 128 || tiles < 256) return a.w_image ? 14 : 22;
-  return 24;
-}
-
-int spgan_nt_wide3_tile_n(const spgan_gemm_nt_args& a) { return spgan_nt_wide3_config(a) == 22 ? 128 : 256; }
-
-bool spgan_nt_wide3_selected(const spgan_gemm_nt_args& a) {
-  static const bool off = getenv("SPGAN_NT_WIDE3") && atoi(getenv("SPGAN_NT_WIDE3")) == 0;
-  if (off || a.tile_hint == 1 || !spgan_nt_wide3_eligible(a)) return false;
-  if (a.tile_hint == 2) return true;
-  // a workgroup per CU at least, and a k-loop worth its ramp (the 128-row split kernel serves the rest); tiles of ONE group, as in
-  // spgan_nt_wide3_config: a grouped launch must pick the kernel, and so the summation order, of its separate passes
-  return (long)((a.p_group_rows > 0 ? a.p_group_rows : a.M) / 256) * (a.N / 128) >= 128 && a.K >= 64;
-}
-
-int spgan_launch_nt_wide3(const spgan_gemm_nt_args& a, hipStream_t s) {
-  if (a.a_mode == SPGAN_A_PLAIN) return launch_epi<SPGAN_A_PLAIN>(a, s);
-  if (a.sp_val) return launch_epi<SPGAN_WIDE_A_SPARSE>(a, s);
-  return launch_epi<SPGAN_A_AFFINE_LRELU>(a, s);
+int spgan_launch_nt_wide3(const spgan_gemm_nt_args& a, int config, hipStream_t s) {
+  if (a.a_mode == SPGAN_A_PLAIN) return launch_epi<SPGAN_A_PLAIN>(a, config, s);
+  if (a.sp_val) return launch_epi<SPGAN_WIDE_A_SPARSE>(a, config, s);
+  return launch_epi<SPGAN_A_AFFINE_LRELU>(a, config, s);
 }

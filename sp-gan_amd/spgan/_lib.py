@@ -25,6 +25,11 @@ class ColTail(C.Structure):
                 ("eps", C.c_float), ("momentum", C.c_float), ("count_rep", C.c_int)]
 
 
+# spgan_gemm_nt_kernel's answers (SPGAN_NT_KERNEL_* of spgan_hip.h)
+NT_KERNEL_K4_STREAM, NT_KERNEL_SMALL, NT_KERNEL_TILE, NT_KERNEL_WIDE, NT_KERNEL_WIDE16, NT_KERNEL_WIDE3 = 1, 2, 3, 4, 5, 6
+NT_PLAN_FIELDS = ("kernel", "invalid", "tile_n", "owns_columns", "cfg", "db", "fast", "operand", "store16", "wide3_cfg")   # spgan_gemm_nt_plan
+
+
 class GemmNTArgs(C.Structure):
     _fields_ = [
         ("A", c_f32p), ("lda", C.c_int),
@@ -215,6 +220,8 @@ SIGNATURES = {
     "spgan_pm_to_cm": (I, [P, I, I, I, P, P]),
     "spgan_concat2": (I, [P, I, P, I, I, P, P]),
     "spgan_gemm_nt": (I, [C.POINTER(GemmNTArgs), P]),
+    "spgan_gemm_nt_kernel": (I, [C.POINTER(GemmNTArgs)]),
+    "spgan_gemm_nt_plan": (I, [C.POINTER(GemmNTArgs), P]),
     "spgan_gemm_nt_col_blocks": (I, [C.POINTER(GemmNTArgs)]),
     "spgan_split_bf16x3_image_bytes": (C.c_size_t, [I, I]),
     "spgan_split_bf16x3_image": (I, [P, I, I, I, P, P]),

@@ -128,10 +128,12 @@ def get_mfma_operands() -> str:
 
 
 # Split-bf16 weight images ("bf16x3" operand mode): the 256-row-tile gemm_nt kernel copies W's three bf16 planes from a pre-split image of W
-# (split_image below: made once per weight and optimiser step) instead of splitting W's fp32 rows again in every workgroup.  ops does not
-# know which operands are weights and when they change -- the provider does (nets.w_image: parameters and their cached transposes, refreshed
-# when the weights' epoch / version moves, all stale images of a network in one launch); None, or a provider returning None: W is split
-# on the fly.  Signature: provider(W) -> uint8 image tensor | None.
+# (split_image below) instead of splitting W's fp32 rows again in every workgroup.  The hook is supplied by the caller: nothing in the
+# package installs one (tests and tools/nt3_bench.py do), and ops neither caches images nor knows when a weight changes -- that is the
+# provider's business.  None, or a provider returning None: W is split on the fly.  Signature: provider(W) -> uint8 image tensor | None.
+# Stream rule: _attach_w_image holds the image only until the wrapper returns, not until the kernel has run.  That is safe only because the
+# image is allocated on the launch stream by the stream-ordered caching allocator (its memory is not handed to another stream's work before
+# the launch that reads it); a provider that makes its images on another stream must keep them alive and ordered itself.
 w_image_provider = None
 
 
@@ -786,10 +788,10 @@ def collapsed_pair_preferred(M: int, K: int) -> bool:
         return False
     key = (int(M), int(K))
     if key not in _PAIR_OK:
-        # the input-gradient launch carries the stored-tile epilogue (gout), which only gemm_wide3.hip has: ask the library whether it runs there
+        # the input-gradient launch carries the stored-tile epilogue (gout), which only gemm_wide3.hip has: ask the library which kernel runs it
         a = GemmNTArgs(); a.mfma_f16 = 2; a.M, a.N, a.K = key[0], key[1], key[1]; a.lda = a.ldw = a.ldy = a.ld_ref = a.ld_rowbias = key[1]
         a.a_mode = A_AFFINE_LRELU; a.p_slope = 0.2; a.epi_mode = EPI_BNBWD; a.rows_per_group = 1
-        _PAIR_OK[key] = bool(_lib.load().spgan_gemm_nt_uses_w_image(C.byref(a)))
+        _PAIR_OK[key] = _lib.load().spgan_gemm_nt_kernel(C.byref(a)) == _lib.NT_KERNEL_WIDE3
     return _PAIR_OK[key]
 
 

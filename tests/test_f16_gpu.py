@@ -502,7 +502,7 @@ WIDE3_SHAPES = [   # M, N, K, what it exercises
 
 def _images(ops):
     """A provider without a cache: every call splits W anew (a cache keyed by address would hand a recycled temporary's image to its successor --
-    the staleness rules are the real provider's business, nets.w_image)."""
+    staleness is the provider's business: the hook is supplied by the caller, nothing in the package installs one)."""
     return lambda Wt: ops.split_image(Wt)
 
 
