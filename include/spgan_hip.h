@@ -1480,6 +1480,37 @@ int spgan_epilogue_backward(const spgan_epilogue_args* a, const float* dy, float
 int spgan_truncation(const float* x, const float* avg, int avg_per_layer, int B, int Lr, int D, int max_layer, float thr, int bwd, float* out,
                      spgan_stream_t s);
 
+/* ----------------------------------------------------------------------------------------
+ * The point-distribution losses of Common/model_utils.py (csrc/point_losses.hip): the `keep` nearest slots of every point's
+ * group, and the repulsion tails over them.  xyz [B,n,3]; val float [B,n,keep], idx int32 [B,n,keep] (cloud-local), coef float [B,n,keep].
+ * Group of point i, slots 0..nsample-1, with dx = p_i - p_j and d2 = (dx*dx + dy*dy) + dz*dz, each operation rounded on its own:
+ *   knn_idx == NULL (ball): the first nsample indices j (ascending) with d2 < radius*radius (STRICT; a float product), every further slot
+ *     repeats the first hit; an empty ball holds point 0 in every slot (spgan_pointops_ballquery with new_xyz = xyz).  5 <= nsample <= 256,
+ *     radius > 0.
+ *   knn_idx int32 [B,n,nsample] (kNN): slot s is knn_idx[b,i,s], as written by spgan_pointops_knnquery.  5 <= nsample <= 200, nsample <= n.
+ * Slot value by metric: 0 d2;  1 (|dx| + |dy|) + |dz|;  2 sqrtf(d2 + 1e-12f), ordered by d2.
+ * Selection: the keep (2..8, <= nsample) smallest slots by (float bits of the value, slot), ascending; duplicated padding slots are slots
+ *   of their own.  val / idx hold the winners' values and point indices.
+ * tail != 0 (terms over the winners 1..keep-1, recomputed in float64 from the coordinates; winner 0 is dropped, its coef is 0):
+ *   1: term = max(0, h - v), coef = -1 where h - v > 0, else 0
+ *   2: w = max(1e-12, v), term = rterm - sqrt(w) * exp(-w / (h*h)), coef = the term's derivative in v where v > 1e-12, else 0
+ *   loss[0] = (float)(sum of all terms / (B*n*(keep-1))): a wave adds its terms in ascending winner order, a workgroup its waves in
+ *   ascending order into partial[g] (float64, spgan_point_losses_partials(B, n) entries), a second launch adds the partials (thread t of
+ *   1024: t, t+1024, .. ascending, then a halving tree) and rounds once.  tail == 0: coef, partial and loss may be NULL; one launch.
+ * spgan_point_losses_bwd: dxyz[b,i] = (gscale ? gscale[0] : 1) * scale * ( sum over t ascending of coef[b,i,t] * g(p_i - p_idx[b,i,t])
+ *   - sum over the slots (i',t) with idx[b,i',t] == i, ascending, of coef[b,i',t] * g(p_i' - p_i) ), g(d) = 2d; sign(d) with sign(0) = 0;
+ *   d / sqrt(d2 + 1e-12) for metric 0; 1; 2.  float64 throughout, rounded once, no atomics.  rowptr / slots given (spgan_gather_csr of idx
+ *   as int64 [B, n*keep], n <= 16384): the incoming terms in ascending slot order over the per-point lists.  NULL: four waves per 64 points
+ *   walk the cloud's index table through LDS, 4096 entries per round, wave w the w-th quarter of each round; the incoming terms are added
+ *   per wave in ascending slot order and the waves' sums in ascending w (any n; the slower route).
+ * Bad sizes return SPGAN_EINVAL before any launch.
+ * ---------------------------------------------------------------------------------------- */
+int spgan_point_losses_partials(int B, int n);
+int spgan_point_losses_fwd(const float* xyz, const int32_t* knn_idx, int B, int n, int nsample, float radius, int metric, int keep, int tail,
+                           double h, double rterm, float* val, int32_t* idx, float* coef, double* partial, float* loss, spgan_stream_t s);
+int spgan_point_losses_bwd(const float* xyz, const int32_t* idx, const float* coef, const float* gscale, float scale, int B, int n, int keep,
+                           int metric, const int32_t* rowptr, const int32_t* slots, float* dxyz, spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

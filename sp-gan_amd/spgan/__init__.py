@@ -24,6 +24,9 @@ from .gan_layers import (AdaptiveInstanceNorm, LayerEpilogue, MinibatchStdDev, N
                          spectral_norm_network)
 from .expansion_penalty import expansionPenaltyFunction, expansionPenaltyModule   # noqa: F401
 from .mds import gather_operation, minimum_density_sample                       # noqa: F401
+from . import model_utils                                                       # noqa: F401
+from .model_utils import (get_cd_loss, get_cd_loss2, get_hausdorff_loss, get_perulsion_loss, get_repulsion_loss, get_repulsion_loss4,   # noqa: F401
+                          get_uniform_loss_knn, group_nearest)
 from .optim import EMA, Adam, StepLR, flatten_module                       # noqa: F401
 from .parallel import DataParallel, init_process_group_from_env, shard_batch   # noqa: F401
 from .train import TrainStep, requires_grad                                # noqa: F401
@@ -37,4 +40,6 @@ __all__ = ["Generator", "Discriminator", "EdgeBlock", "AdaptivePointNorm", "get_
            "pointnet2_utils", "pointnet2_modules", "pytorch_utils",
            "gan_layers", "SpectralNorm", "spectral_norm", "spectral_norm_network", "snconv2d", "snlinear", "l2normalize", "MinibatchStdDev",
            "StddevLayer", "PixelNorm", "PixelwiseNorm", "NoiseLayer", "NoiseInjection", "LayerEpilogue", "AdaptiveInstanceNorm", "WScaleLayer",
-           "Truncation"]
+           "Truncation",
+           "model_utils", "get_repulsion_loss", "get_repulsion_loss4", "get_perulsion_loss", "get_uniform_loss_knn", "get_cd_loss", "get_cd_loss2",
+           "get_hausdorff_loss", "group_nearest"]

@@ -477,6 +477,9 @@ SIGNATURES = {
     "spgan_epilogue_forward": (I, [C.POINTER(EpilogueArgs), P, P]),
     "spgan_epilogue_backward": (I, [C.POINTER(EpilogueArgs), P, P, P, P, P, P, I, P, P]),
     "spgan_truncation": (I, [P, P, I, I, I, I, I, F, I, P, P]),
+    "spgan_point_losses_partials": (I, [I, I]),
+    "spgan_point_losses_fwd": (I, [P, P, I, I, I, F, I, I, I, C.c_double, C.c_double, P, P, P, P, P, P]),
+    "spgan_point_losses_bwd": (I, [P, P, P, P, F, I, I, I, I, P, P, P, P]),
 }
 
 _lib = None
