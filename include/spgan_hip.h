@@ -1511,6 +1511,42 @@ int spgan_point_losses_fwd(const float* xyz, const int32_t* knn_idx, int B, int 
 int spgan_point_losses_bwd(const float* xyz, const int32_t* idx, const float* coef, const float* gscale, float scale, int B, int n, int keep,
                            int metric, const int32_t* rowptr, const int32_t* slots, float* dxyz, spgan_stream_t s);
 
+/* ----------------------------------------------------------------------------------------
+ * The approxmatch earth mover's distance (StructuralLosses.match_cost, tf_approxmatch; csrc/approxmatch.hip).
+ * xyz1 [B,n,3] (k), xyz2 [B,m,3] (l), float32; the larger of n, m a multiple of the smaller; B <= 65535.  stride1 is xyz1's batch stride
+ * in floats: n*3, or 0 (one cloud against B clouds).  With d2 = |xyz1[k] - xyz2[l]|^2, multiL = max(n,m)/n, multiR = max(n,m)/m:
+ *   remainL = multiL, remainR = multiR;  for i = 0..9 (j = 7..-2), level = -(4^j), level(j = -2) = 0, E = exp(level * d2):
+ *     ratioL[i][k] = remainL[k] / (1e-9 + sum_l E * remainR[l])
+ *     sumr[l] = remainR[l] * sum_k E * ratioL[i][k];  ratioR[i][l] = min(remainR[l] / (sumr[l] + 1e-9), 1) * remainR[l];
+ *     remainR[l] = max(0, remainR[l] - sumr[l])
+ *     remainL[k] = max(0, remainL[k] - ratioL[i][k] * sum_l E * ratioR[i][l]);  cost += ratioL[i][k] * sum_l E * ratioR[i][l] * sqrt(d2)
+ *   match(k,l) = sum_i E_i * ratioL[i][k] * ratioR[i][l] is never stored by the forward: it writes cost [B] and the records
+ *   ratioL [B,10,n], ratioR [B,10,m].  ws: spgan_approxmatch_ws_bytes(B, n, m) bytes, 8-byte aligned.  d2 and E are float32; remainL,
+ *   remainR, the ratios of the level in flight, the row costs and every sum are float64 (the records are their float32 roundings).
+ *   23 launches, no host synchronisation, no atomics; every sum has a fixed order (a lane's four interleaved accumulators over
+ *   ascending points, then the block's waves ascending).
+ *   waves: 0 or 4 (four waves share a block's 64 stationary points), or 1 (the measured alternative, one wave per block).
+ * spgan_approxmatch_bwd: grad_xyz1[k] = grad_cost[b] * sum_l match(k,l) * (xyz1[k] - xyz2[l]) / max(sqrt(d2), 1e-20), grad_xyz2[l] the
+ *   negated sum over k; match is recomputed from the records and held constant.  Either output may be NULL; one launch each.
+ * spgan_approxmatch_plan: match [B,m,n], entry [b,l,k] (tf_approxmatch.approx_match's layout), from the records; m <= 65535.
+ * spgan_match_cost_dense_fwd / _bwd: cost [B] = sum match[b,l,k] * sqrt(d2) and the same two gradients from a caller's dense plan
+ *   (ws: B*m doubles; spgan_approxmatch_ws_bytes covers it); sums in float64.
+ * Bad sizes and null pointers return SPGAN_EINVAL before any launch.
+ * ---------------------------------------------------------------------------------------- */
+int spgan_approxmatch_levels(void);
+int spgan_approxmatch_tile(void);
+size_t spgan_approxmatch_ws_bytes(int B, int n, int m);
+int spgan_approxmatch_fwd(const float* xyz1, long stride1, const float* xyz2, int B, int n, int m, int waves, float* cost, float* ratioL,
+                          float* ratioR, void* ws, size_t ws_bytes, spgan_stream_t s);
+int spgan_approxmatch_bwd(const float* xyz1, long stride1, const float* xyz2, int B, int n, int m, const float* ratioL, const float* ratioR,
+                          const float* grad_cost, float* grad_xyz1, float* grad_xyz2, spgan_stream_t s);
+int spgan_approxmatch_plan(const float* xyz1, long stride1, const float* xyz2, int B, int n, int m, const float* ratioL, const float* ratioR,
+                           float* match, spgan_stream_t s);
+int spgan_match_cost_dense_fwd(const float* xyz1, const float* xyz2, const float* match, int B, int n, int m, float* cost, void* ws,
+                               size_t ws_bytes, spgan_stream_t s);
+int spgan_match_cost_dense_bwd(const float* xyz1, const float* xyz2, const float* match, int B, int n, int m, const float* grad_cost,
+                               float* grad_xyz1, float* grad_xyz2, spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,8 @@ Importing the package does not touch the GPU; the shared library is loaded on fi
 absence is a hard error (there is no CPU fallback).
 """
 from . import block_tail, dataset, edge_conv, edge_max, edge_rank, edge_weight, edge_window, fixture_rng, metrics, ops, pointconv_util, pointnet_util, point_attn, gc_attn, sampling  # noqa: F401
-from . import compat, fpd, pointops                                       # noqa: F401
+from . import approxmatch, compat, fpd, pointops                           # noqa: F401
+from .approxmatch import MatchCostFunction, approx_match, emd_approx_match, match_cost, match_cost_dense   # noqa: F401
 from . import pointnet2_modules, pointnet2_utils, pytorch_utils            # noqa: F401
 from .capture import CapturedBody                                          # noqa: F401
 from .losses import GradientPenalty, dis_loss, gen_loss                    # noqa: F401
@@ -25,8 +26,8 @@ from .gan_layers import (AdaptiveInstanceNorm, LayerEpilogue, MinibatchStdDev, N
 from .expansion_penalty import expansionPenaltyFunction, expansionPenaltyModule   # noqa: F401
 from .mds import gather_operation, minimum_density_sample                       # noqa: F401
 from . import model_utils                                                       # noqa: F401
-from .model_utils import (get_cd_loss, get_cd_loss2, get_hausdorff_loss, get_perulsion_loss, get_repulsion_loss, get_repulsion_loss4,   # noqa: F401
-                          get_uniform_loss_knn, group_nearest)
+from .model_utils import (get_cd_loss, get_cd_loss2, get_emd_loss, get_hausdorff_loss, get_perulsion_loss, get_repulsion_loss,   # noqa: F401
+                          get_repulsion_loss4, get_uniform_loss_knn, group_nearest)
 from .optim import EMA, Adam, StepLR, flatten_module                       # noqa: F401
 from .parallel import DataParallel, init_process_group_from_env, shard_batch   # noqa: F401
 from .train import TrainStep, requires_grad                                # noqa: F401
@@ -42,4 +43,5 @@ __all__ = ["Generator", "Discriminator", "EdgeBlock", "AdaptivePointNorm", "get_
            "StddevLayer", "PixelNorm", "PixelwiseNorm", "NoiseLayer", "NoiseInjection", "LayerEpilogue", "AdaptiveInstanceNorm", "WScaleLayer",
            "Truncation",
            "model_utils", "get_repulsion_loss", "get_repulsion_loss4", "get_perulsion_loss", "get_uniform_loss_knn", "get_cd_loss", "get_cd_loss2",
-           "get_hausdorff_loss", "group_nearest"]
+           "get_hausdorff_loss", "group_nearest", "get_emd_loss",
+           "approxmatch", "MatchCostFunction", "approx_match", "match_cost", "match_cost_dense", "emd_approx_match"]

@@ -480,6 +480,14 @@ SIGNATURES = {
     "spgan_point_losses_partials": (I, [I, I]),
     "spgan_point_losses_fwd": (I, [P, P, I, I, I, F, I, I, I, C.c_double, C.c_double, P, P, P, P, P, P]),
     "spgan_point_losses_bwd": (I, [P, P, P, P, F, I, I, I, I, P, P, P, P]),
+    "spgan_approxmatch_levels": (I, []),
+    "spgan_approxmatch_tile": (I, []),
+    "spgan_approxmatch_ws_bytes": (SZ, [I, I, I]),
+    "spgan_approxmatch_fwd": (I, [P, LG, P, I, I, I, I, P, P, P, P, SZ, P]),
+    "spgan_approxmatch_bwd": (I, [P, LG, P, I, I, I, P, P, P, P, P, P]),
+    "spgan_approxmatch_plan": (I, [P, LG, P, I, I, I, P, P, P, P]),
+    "spgan_match_cost_dense_fwd": (I, [P, P, P, I, I, I, P, P, SZ, P]),
+    "spgan_match_cost_dense_bwd": (I, [P, P, P, I, I, I, P, P, P, P]),
 }
 
 _lib = None

@@ -8,6 +8,8 @@
     from CD_EMD.cd.chamferdist import ChamferDistance as CD                           # -> spgan.metrics.ChamferDistance
     from pointnet2.pointnet2_modules import PointnetSAModule, PointnetSAModuleMSG     # model.py / Generator.py / modules.py (commented there)
     from metrics.pointnet2 import pointnet2_utils, pytorch_utils                      # -> spgan.pointnet2_utils, spgan.pytorch_utils
+    from StructuralLosses.match_cost import match_cost                                # metrics/evaluation_metrics.py:9 -> spgan.approxmatch
+    from metrics.StructuralLosses.nn_distance import nn_distance                      # metrics/evaluation_metrics.py:10 -> spgan.metrics
 
 `install()` puts lightweight module objects into sys.modules; each forwards attribute look-ups to the spgan module behind it, so the names
 resolve to the very objects of this package.  A name that already resolves to a real module (one in sys.modules, or one the import system
@@ -54,6 +56,12 @@ STAND_INS: Dict[str, Optional[str]] = {
     "metrics.pointnet2_ops.pointnet2_modules": "spgan.pointnet2_modules",
     "metrics.pointnet2_ops.pytorch_utils": "spgan.pytorch_utils",
     "metrics.pointnet2_utils": "spgan.pointnet2_utils",
+    "StructuralLosses": None,
+    "StructuralLosses.match_cost": "spgan.approxmatch",
+    "StructuralLosses.nn_distance": "spgan.metrics",
+    "metrics.StructuralLosses": None,
+    "metrics.StructuralLosses.match_cost": "spgan.approxmatch",
+    "metrics.StructuralLosses.nn_distance": "spgan.metrics",
 }
 # children that are NOT set as attributes of their parent: `from CD_EMD.cd.chamferdist import ChamferDistance` is the class, as the
 # reference's own __init__ arranges

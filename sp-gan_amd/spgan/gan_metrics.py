@@ -21,8 +21,9 @@ tree and is not provided, so by default compute_all_metrics on 2-D inputs and co
 NotImplementedError as before.  compute_all_metrics(..., fpd=True) on 2-D feature rows runs the reference's branch (l2 distances over
 the features, FPD filled in); compute_all_metrics_train(..., model=<module>, use_FPD_JSD=True) takes the caller's network, computes its
 activations, JSD and FPD (the reference computes the activations and leaves its FPD line commented out, so its FPD stays 0).
-"EMD" dispatches to spgan.metrics.pairwise_emd (the tree's auction, mean over the points of sqrt(dist)), not the reference's emd_approx
-of this module (300 iterations, mean of the squared distances over a whole chunk).
+"EMD" dispatches to spgan.metrics.pairwise_emd, not the reference's emd_approx of this module (300 iterations, mean of the squared
+distances over a whole chunk): with emd="auction" (the default) the tree's auction, mean over the points of sqrt(dist); with
+emd="match_cost" the approxmatch EMD of StructuralLosses.match_cost (spgan.approxmatch), divided by the point count.
 """
 from __future__ import annotations
 
@@ -80,16 +81,16 @@ def pairwise_local_CD(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int, dist
     return torch.stack([m[:, lo:lo + batch_size].sum(dim=1) for lo in range(0, R, batch_size)], dim=1)
 
 
-def pairwise_dists(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int, dist_type: str = "l2") -> Tensor:
+def pairwise_dists(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int, dist_type: str = "l2", emd: str = "auction") -> Tensor:
     """GAN_metrics.py:548-559: the [S,R] matrix for "CD" (mean_i min_j + mean_j min_i), "CD_M" / "CD_C" (the local terms, per pair;
-    see the module note), "EMD" (spgan.metrics.pairwise_emd) and anything else as "l2" on feature rows."""
+    see the module note), "EMD" (spgan.metrics.pairwise_emd with its `emd` route) and anything else as "l2" on feature rows."""
     sample_pcs, ref_pcs = _dev(sample_pcs), _dev(ref_pcs)
     if dist_type == "CD":
         return pairwise_cd(sample_pcs, ref_pcs)
     if dist_type in ("CD_M", "CD_C"):
         return pairwise_local_cd(sample_pcs, ref_pcs)[..., _local_term(dist_type)].contiguous()
     if dist_type == "EMD":
-        return pairwise_emd(sample_pcs, ref_pcs, batch_size)
+        return pairwise_emd(sample_pcs, ref_pcs, batch_size, emd=emd)
     return pairwise_simple(sample_pcs, ref_pcs, batch_size, "l2")
 
 

@@ -13,8 +13,10 @@
 
   emdFunction / emdModule                the auction EMD of metrics/CD_EMD/emd_/emd_module.py:33-85 (over emd_cuda.cu)
   emd_approx, pairwise_emd, EMD_CD,      the EMD half of metrics/evaluation_metrics.py:26-35,52-126,176-207.  There `emd_approx`
-  compute_all_metrics                    calls StructuralLosses.match_cost, an extension that is NOT part of the reference tree;
-                                         here it is the tree's own auction module: mean over the points of sqrt(dist).
+  compute_all_metrics                    calls StructuralLosses.match_cost, an extension that is not part of the reference tree.
+                                         emd="auction" (the default) is the tree's own auction module, mean over the points of
+                                         sqrt(dist); emd="match_cost" is that extension's algorithm (spgan.approxmatch over
+                                         csrc/approxmatch.hip), the quantity of the published EMD tables.
 
 The distance searches, the all-pairs Chamfer matrix, the occupancy-grid statistics and the auction are HIP kernels
 (`csrc/metrics.hip`, `csrc/emd.hip`); what remains here are reductions over the [S,R] matrices and the grid histograms (a few
@@ -31,6 +33,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib
+from .approxmatch import emd_approx_match
 from .local_cd import ChamferLoss, knn_moments, local_CD, pairwise_local_cd  # noqa: F401
 from .ops import _f32, _p, _s, check
 
@@ -142,17 +145,40 @@ class emdModule(nn.Module):
         return emdFunction.apply(input1, input2, eps, iters)
 
 
-def emd_approx(sample: Tensor, ref: Tensor, eps: float = 0.005, iters: int = 50) -> Tensor:
-    """Per-pair EMD / N (evaluation_metrics.py:26-35), [B]: mean over the points of the distance to the assigned point."""
+EMD_ROUTES = ("auction", "match_cost")
+
+
+def _emd_route(emd: str) -> bool:
+    """-> True for the approxmatch route."""
+    if emd not in EMD_ROUTES:
+        raise ValueError("emd must be one of %s, got %r" % (EMD_ROUTES, emd))
+    return emd == "match_cost"
+
+
+def emd_approx(sample: Tensor, ref: Tensor, eps: float = 0.005, iters: int = 50, emd: str = "auction") -> Tensor:
+    """Per-pair EMD / N (evaluation_metrics.py:26-35), [B]: mean over the points of the distance to the assigned point ("auction"), or
+    StructuralLosses.match_cost / N ("match_cost": spgan.approxmatch.emd_approx_match; eps and iters are the auction's)."""
+    if _emd_route(emd):
+        return emd_approx_match(sample, ref)
     dist, _ = emdFunction.apply(sample, ref, eps, iters)
     return dist.sqrt().mean(dim=1)
 
 
-def pairwise_emd(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int = 512, eps: float = 0.005, iters: int = 50) -> Tensor:
+def pairwise_emd(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int = 512, eps: float = 0.005, iters: int = 50,
+                 emd: str = "auction") -> Tensor:
     """[S,R] matrix of emd_approx over all pairs (the EMD half of _pairwise_EMD_CD_, evaluation_metrics.py:89-126), `batch_size`
-    pairs per auction launch sequence."""
+    pairs per auction launch sequence.  emd="match_cost": every sample cloud is read in place against `batch_size` reference clouds at
+    a time (a batch stride of 0, as the reference expands it, but without the copy)."""
     a, b = _cloud(sample_pcs, "sample_pcs"), _cloud(ref_pcs, "ref_pcs")
     S, R = a.shape[0], b.shape[0]
+    if _emd_route(emd):
+        out = torch.empty((S, R), dtype=torch.float32, device=a.device)
+        with torch.no_grad():
+            for s in range(S):
+                for lo in range(0, R, batch_size):
+                    refs = b[lo:lo + batch_size]
+                    out[s, lo:lo + batch_size] = emd_approx_match(a[s:s + 1].expand(refs.shape[0], -1, -1), refs)
+        return out
     out = torch.empty((S * R,), dtype=torch.float32, device=a.device)
     si = torch.arange(S, device=a.device).repeat_interleave(R)
     ri = torch.arange(R, device=a.device).repeat(S)
@@ -161,11 +187,12 @@ def pairwise_emd(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int = 512, eps
     return out.view(S, R)
 
 
-def EMD_CD(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int = 512, reduced: bool = True) -> Dict[str, Tensor]:
-    """evaluation_metrics.py:52-86: Chamfer and EMD between corresponding clouds."""
+def EMD_CD(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int = 512, reduced: bool = True, emd: str = "auction") -> Dict[str, Tensor]:
+    """evaluation_metrics.py:52-86: Chamfer and EMD between corresponding clouds (emd: see emd_approx)."""
     dl, dr = nn_distance(sample_pcs, ref_pcs)
     cd = dl.mean(dim=1) + dr.mean(dim=1)
-    emd = torch.cat([emd_approx(sample_pcs[lo:lo + batch_size], ref_pcs[lo:lo + batch_size]) for lo in range(0, sample_pcs.shape[0], batch_size)])
+    emd = torch.cat([emd_approx(sample_pcs[lo:lo + batch_size], ref_pcs[lo:lo + batch_size], emd=emd)
+                     for lo in range(0, sample_pcs.shape[0], batch_size)])
     return {"MMD-CD": cd.mean() if reduced else cd, "MMD-EMD": emd.mean() if reduced else emd}
 
 
@@ -262,12 +289,12 @@ def jsd_between_point_cloud_sets(sample_pcs: Tensor, ref_pcs: Tensor, resolution
     return jensen_shannon_divergence(sample_grid_var, ref_grid_var)
 
 
-def compute_all_metrics(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int = 512) -> Dict[str, Tensor]:
-    """evaluation_metrics.py:176-207: MMD / COV / 1-NNA for both Chamfer and EMD."""
+def compute_all_metrics(sample_pcs: Tensor, ref_pcs: Tensor, batch_size: int = 512, emd: str = "auction") -> Dict[str, Tensor]:
+    """evaluation_metrics.py:176-207: MMD / COV / 1-NNA for both Chamfer and EMD (emd: see emd_approx)."""
     res = compute_all_metrics_cd(sample_pcs, ref_pcs)
-    M_rs = pairwise_emd(ref_pcs, sample_pcs, batch_size)
+    M_rs = pairwise_emd(ref_pcs, sample_pcs, batch_size, emd=emd)
     res.update({"%s-EMD" % k: v for k, v in lgan_mmd_cov(M_rs.t()).items()})
-    M_rr, M_ss = pairwise_emd(ref_pcs, ref_pcs, batch_size), pairwise_emd(sample_pcs, sample_pcs, batch_size)
+    M_rr, M_ss = pairwise_emd(ref_pcs, ref_pcs, batch_size, emd=emd), pairwise_emd(sample_pcs, sample_pcs, batch_size, emd=emd)
     res.update({"1-NN-EMD-%s" % k: v for k, v in knn(M_rr, M_rs, M_ss, 1, sqrt=False).items() if "acc" in k})
     return res
 

@@ -1,7 +1,7 @@
 """The point-distribution losses of Common/model_utils.py over the HIP kernels of csrc/point_losses.hip.
 
     from spgan.model_utils import get_repulsion_loss, get_repulsion_loss4, get_perulsion_loss, get_uniform_loss_knn
-    from spgan.model_utils import get_cd_loss, get_cd_loss2, get_hausdorff_loss, group_nearest
+    from spgan.model_utils import get_cd_loss, get_cd_loss2, get_hausdorff_loss, get_emd_loss, group_nearest
 
 The reference file is TensorFlow 1 over custom ops that are not part of its tree; the signatures here are its own, the semantics of the
 missing ops are those of this project's ball query and kNN.  pred / gt are [B,N,3] float32 device tensors; every loss is
@@ -23,6 +23,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from .approxmatch import match_cost
 from .metrics import nn_distance
 from .ops import _f32, _p, _s, check
 
@@ -207,3 +208,14 @@ def get_hausdorff_loss(pred: Tensor, gt: Tensor, radius: float, forward_weight: 
         b = torch.where(b < threshold, b, torch.zeros_like(b))
     cd = (forward_weight * f.amax(dim=1) + b.amax(dim=1)) / radius
     return cd.amax(), None
+
+
+def get_emd_loss(pcd1: Tensor, pcd2: Tensor, radius) -> Tensor:
+    """model_utils.py:281-287: mean_b of match_cost(pcd1, pcd2) / radius / N, the approxmatch EMD of tf_approxmatch (spgan.approxmatch:
+    fused, the [B,N,N] plan that the reference's approx_match returns is never formed).  `radius` is a float or a [B] tensor; the two
+    clouds must have the same point count.  The reference's `_get_emd_loss` (:290-301) unpacks two results from an op that returns one
+    and cannot run there; it is not provided."""
+    if pcd1.dim() != 3 or pcd2.dim() != 3 or pcd1.shape[1] != pcd2.shape[1]:
+        raise ValueError("pcd1 and pcd2 must be [B, N, 3] with the same N, got %s and %s" % (tuple(pcd1.shape), tuple(pcd2.shape)))
+    cost = match_cost(pcd1, pcd2) / radius
+    return (cost / float(pcd1.shape[1])).mean()
