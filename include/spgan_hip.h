@@ -258,7 +258,7 @@ typedef struct spgan_gemm_tn_args {
   const float* p_scale; const float* p_shift; float p_slope;
   const int32_t* e_idx; int e_k; const float* e_bias;
   float beta;
-  float* ws; size_t ws_bytes; /* >= spgan_gemm_tn_ws_bytes(M,Na,Nb) */
+  float* ws; size_t ws_bytes; /* >= spgan_gemm_tn_ws_bytes_lp(M,Na,Nb,mfma_lp) */
   /* Optional prologue on A (per column of A): a = A*a_scale[c] + a_shift[c] + (a_sp_arg[b,c]==m ? a_sp_val[b,c] : 0), b = m / a_sp_rows.
    * a_scale == NULL: A is used as is. */
   const float* a_scale; const float* a_shift; const float* a_sp_val; const int32_t* a_sp_arg; int a_sp_rows;
@@ -272,16 +272,17 @@ typedef struct spgan_gemm_tn_args {
    * 2: every fp32 operand value split exactly into three bfloat16 terms, the six leading cross products on the bf16 matrix pipe, fp32
    * accumulation -- fp32-equivalent products (dropped terms <= 2^-26 relative), as spgan_gemm_nt_args.mfma_f16 == 2.  Honoured where the output
    * tiles as 256 x 256, 256 x 128 or 128 x 256 (Na, Nb multiples of 128, not both odd multiples), M % 32 == 0, fp32-stored operands, b_mode PLAIN /
-   * AFFINE_LRELU with slopes in [0, 1]: csrc/gemm_tn_wide3.hip, with its own split plan (spgan_gemm_tn_splits_lp / _ws_bytes_lp below); every
-   * other problem runs the exact fp32 kernel on that plan. */
+   * AFFINE_LRELU with slopes in [0, 1]: csrc/gemm_tn_wide3.hip, with its own split (spgan_gemm_tn_splits_lp / _ws_bytes_lp below, from the
+   * shape alone); a problem of such a shape that the kernel cannot run (spgan_gemm_tn_kernel tells) runs the exact fp32 kernel on that split. */
   int mfma_lp;
   /* A2 != NULL (needs a_scale, a_shift; not with a_sp_val): a = A*a_scale[c] + A2*a_scale2[c] + a_shift[c] -- the same two-tensor
    * operand as spgan_gemm_nt_args.A2, on the A side of the weight-gradient product. */
   const float* A2; int lda2; const float* a_scale2;
   /* != NULL: also write the column sums of the (transformed) A operand over the rows of every split: a_colsum_ws [splits, Na]
-   * (splits = spgan_gemm_tn_splits(M, Na, Nb)); their fixed-order sum over the splits -- e.g. one more entry (Na = 1, Nb = Na) of
+   * (splits = spgan_gemm_tn_splits_lp(M, Na, Nb, mfma_lp)); their fixed-order sum over the splits -- e.g. one more entry (Na = 1, Nb = Na) of
    * spgan_splitk_reduce_multi -- is colsum(A): the bias gradient that belongs to this weight gradient, without a pass of its own.
-   * Not with a_sp_val, not on the Na / Nb <= 4 streaming path. */
+   * Not with a_sp_val.  The streaming kernel has no such by-product: a block that carries a_colsum_ws never runs it, so ask
+   * spgan_gemm_tn_kernel BEFORE attaching it and attach it only where the answer is not SPGAN_TN_KERNEL_SKINNY. */
   float* a_colsum_ws;
   /* a_lrelu = 1 (needs a_scale, a_shift; not with A2 / a_sp_val): the A-side prologue is a = lrelu(A*a_scale[c] + a_shift[c], a_slope)
    * -- a BatchNorm + LeakyReLU'd activation as the A operand without materialising it (the Gram matrix a^T a of the collapsed
@@ -314,6 +315,15 @@ size_t spgan_gemm_tn_ws_bytes(int M, int Na, int Nb);
 size_t spgan_gemm_tn_ws_bytes_lp(int M, int Na, int Nb, int mfma_lp);
 int spgan_gemm_tn_splits_lp(int M, int Na, int Nb, int mfma_lp);
 int spgan_gemm_tn(const spgan_gemm_tn_args* a, spgan_stream_t s);
+/* The kernel family spgan_gemm_tn runs for this block (0: a == NULL): the one decision (csrc/gemm_tn_plan.hpp) that the launch executes and
+ * that the queries above and below read.  None of them reads through a pointer of the block. */
+enum { SPGAN_TN_KERNEL_SKINNY = 1, SPGAN_TN_KERNEL_TILE = 2, SPGAN_TN_KERNEL_LP = 3, SPGAN_TN_KERNEL_WIDE3 = 4 };
+int spgan_gemm_tn_kernel(const spgan_gemm_tn_args* a);
+/* The whole plan as integers, for tests and tools: out[0..8] = kernel, invalid (16-bit stored operands that no kernel takes: the launch
+ * returns SPGAN_EINVAL), splits, rows per split, the B-tile width 128 / 64 / 32 (TILE, LP), fast (vector loads), narrow_b (SKINNY: B is the
+ * narrow side), the split-bf16 tile configuration 24 / 22 / 14 (WIDE3, else 0), sparse_rows (the sparse-addend launch follows). */
+#define SPGAN_TN_PLAN_FIELDS 9
+int spgan_gemm_tn_plan(const spgan_gemm_tn_args* a, int32_t* out);
 /* `count` (<= 4) streaming products with a narrow B (Nb <= 4: the weight gradient of D's first conv against the three input coordinates) of ONE
  * shape as one launch, partials only (defer_reduce != 0 required; summed by spgan_splitk_reduce_multi): real / fake / double-backward pass of a
  * grouped D step.  A plain or two-tensor (A2) A operand. */

@@ -28,6 +28,7 @@
 #include "common.hpp"
 #include "adain_epi.hpp"
 #include "gemm_nt_plan.hpp"
+#include "gemm_tn_plan.hpp"
 #include "gemm_wide.hpp"
 #include "gemm_tn_wide3.hpp"
 #include "sparse_rows.hpp"
@@ -1311,9 +1312,7 @@ int launch_nt(const spgan_gemm_nt_args& a, const spgan_nt_plan& pl, hipStream_t 
 }
 
 // ------------------------------------------------------------------------------------------ gemm_tn
-constexpr int TKM = 32;  // m-rows per staging step (= MFMA k-steps * 2 between two barriers)
-constexpr int TA = 128;  // output rows (columns of A) per workgroup
-
+// (TKM m-rows per staging step, TA output rows per workgroup: gemm_tn_plan.hpp, where the split rule needs them)
 // Column-constant prologue parameters of this thread's staging slot (hoisted out of the m loop).
 struct ColPro {
   float4 sc, sh, eb;
@@ -1894,30 +1893,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_multi_kernel(const spgan_sp
   }
 }
 
-inline int tn_tb(int Nb) { return Nb > 64 ? 128 : (Nb > 32 ? 64 : 32); }
-
-// Split choice: about two workgroups per CU in total, at least 256 m-rows each.
-// One side of the product has <= 4 columns (the weight gradients of the 3-channel layers: D's first conv, the generator's tail.4
-// and pc inputs): nothing for the matrix cores to do -- gemm_tn_skinny_kernel streams the wide operand once.
-inline bool tn_skinny(int Na, int Nb) { return (Na <= 4 || Nb <= 4) && Na <= 2048 && Nb <= 2048; }
-
-inline void tn_plan(int M, int Na, int Nb, int* splits, int* rows) {
-  if (tn_skinny(Na, Nb)) {
-    int r = cdiv(cdiv(M, 1024), TKM) * TKM;  // <= 1024 partials, each over a multiple of TKM rows (the MFMA kernel may have to serve the plan)
-    if (r < 128) r = 128;
-    *rows = r;
-    *splits = cdiv(M, r);
-    return;
-  }
-  const int tiles = cdiv(Na, TA) * cdiv(Nb, tn_tb(Nb));
-  int want = cdiv(512, tiles);
-  int r = cdiv(M, want);
-  if (r < 64) r = 64;  // two staging steps: short reductions (M ~ 1000: the K x K products of the collapsed backward) are latency-bound, spread them
-  r = cdiv(r, TKM) * TKM;
-  *rows = r;
-  *splits = cdiv(M, r);
-}
-
 // out[split][Na][Nb] partials of A^T B when A or B has <= 4 columns: 64 columns of the wide operand x 4 row-lanes per workgroup,
 // the narrow operand's row is a broadcast load; the four row-lanes are summed in a fixed order.
 template <bool NARROW_B>
@@ -1997,59 +1972,32 @@ inline void launch_reduce(const spgan_gemm_tn_args& a, int splits, hipStream_t s
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(n, 64)), dim3(256), 0, s, a.ws, splits, a.Na, a.Nb, a.C, a.ldc, a.beta);
 }
 
-// The plan of a launch with operand mode lp: the split-bf16 kernel (lp == 2, gemm_tn_wide3.hip) has larger output tiles, hence its own plan for
-// the shapes it takes (from the shape alone: a problem it then cannot run -- alignment -- runs the plan on the kernels below)
-inline void tn_plan_lp(int M, int Na, int Nb, int lp, int* splits, int* rows) {
-  if (lp == 2 && !tn_skinny(Na, Nb) && spgan_tn_wide3_config(M, Na, Nb)) spgan_tn_wide3_plan(M, Na, Nb, splits, rows);
-  else tn_plan(M, Na, Nb, splits, rows);
+// Executes the plan (gemm_tn_plan.hpp): the if constexpr guards only keep forms no plan names from being instantiated.
+template <int BMODE, int CFG>
+void launch_tn_tile(const spgan_gemm_tn_args& a, const spgan_tn_plan& pl, hipStream_t s) {
+  const dim3 grid(cdiv(a.Na, TA) * cdiv(a.Nb, pl.tile_b), pl.splits);
+  if (pl.kernel == TN_LP) hipLaunchKernelGGL((gemm_tn_lp_kernel<BMODE, CFG>), grid, dim3(256), 0, s, a, pl.rows);
+  else if (pl.fast) hipLaunchKernelGGL((gemm_tn_kernel<BMODE, CFG, 1>), grid, dim3(256), 0, s, a, pl.rows);
+  else hipLaunchKernelGGL((gemm_tn_kernel<BMODE, CFG, 0>), grid, dim3(256), 0, s, a, pl.rows);
 }
 
 template <int BMODE>
-int launch_tn(const spgan_gemm_tn_args& a, hipStream_t s) {
-  int splits, rows;
-  tn_plan_lp(a.M, a.Na, a.Nb, a.mfma_lp, &splits, &rows);
-  if constexpr (BMODE != SPGAN_A_EDGE) {
-    if (!tn_skinny(a.Na, a.Nb) && spgan_tn_wide3_eligible(a)) {   // split-bf16 operands: the fp32-equivalent product on the bf16 matrix pipe
-      const int rc = spgan_launch_tn_wide3(a, splits, rows, s);
+int launch_tn(const spgan_gemm_tn_args& a, const spgan_tn_plan& pl, hipStream_t s) {
+  if (pl.kernel == TN_WIDE3) {
+    if constexpr (BMODE != SPGAN_A_EDGE) {
+      const int rc = spgan_launch_tn_wide3(a, pl.wide3_cfg, pl.splits, pl.rows, s);
       if (rc != SPGAN_OK) return rc;
-      if (!a.defer_reduce) launch_reduce(a, splits, s);
-      if (a.a_sp_val) hipLaunchKernelGGL((tn_sparse_rows_kernel<BMODE>), dim3(a.Na), dim3(256), 0, s, a);
-      return spgan_launch_status();
     }
-  }
-  // the streaming kernels: no prologues -- except the two-tensor A operand on the wide side (a lazy BatchNorm-backward tensor against 3 input columns)
-  if (BMODE == SPGAN_A_PLAIN && tn_skinny(a.Na, a.Nb) && !a.a_colsum_ws && !a.b_half &&
-      (!a.a_scale || (a.A2 && a.Nb <= 4 && !a.a_lrelu && !a.a_sp_val))) {
-    const bool narrow_b = a.Nb <= 4;
-    const dim3 g(cdiv(narrow_b ? a.Na : a.Nb, 64), splits);
-    if (narrow_b) hipLaunchKernelGGL((gemm_tn_skinny_kernel<true>), g, dim3(256), 0, s, a, rows);
-    else hipLaunchKernelGGL((gemm_tn_skinny_kernel<false>), g, dim3(256), 0, s, a, rows);
-    if (!a.defer_reduce) launch_reduce(a, splits, s);
-    return spgan_launch_status();
-  }
-  if (a.b_half && (BMODE != SPGAN_A_PLAIN || a.mfma_lp != 1 || a.a_sp_val)) return SPGAN_EINVAL;  // fp16-stored B: the bf16 kernel only
-  if (a.a_half && (a.mfma_lp != 1 || a.a_sp_val || tn_skinny(a.Na, a.Nb))) return SPGAN_EINVAL;    // 16-bit stored A (/A2): likewise
-  const int TB = tn_tb(a.Nb);
-  const dim3 grid(cdiv(a.Na, TA) * cdiv(a.Nb, TB), splits);
-  const bool fast = (a.Na % 4 == 0) && (a.Nb % 4 == 0) && (a.lda % 4 == 0) && (a.ldb % 4 == 0) && al16(a.A) && al16(a.B) &&
-                    (!a.A2 || (al16(a.A2) && a.lda2 % 4 == 0));
-  if ((a.b_half || a.a_half) && !fast) return SPGAN_EINVAL;
-  if (fast && a.mfma_lp == 1) {  // bf16 operands (aligned problems only; others keep the fp32 kernel)
-    if (TB == 128) hipLaunchKernelGGL((gemm_tn_lp_kernel<BMODE, 0>), grid, dim3(256), 0, s, a, rows);
-    else if (TB == 64) hipLaunchKernelGGL((gemm_tn_lp_kernel<BMODE, 1>), grid, dim3(256), 0, s, a, rows);
-    else hipLaunchKernelGGL((gemm_tn_lp_kernel<BMODE, 2>), grid, dim3(256), 0, s, a, rows);
-  } else if (fast) {
-    if (TB == 128) hipLaunchKernelGGL((gemm_tn_kernel<BMODE, 0, 1>), grid, dim3(256), 0, s, a, rows);
-    else if (TB == 64) hipLaunchKernelGGL((gemm_tn_kernel<BMODE, 1, 1>), grid, dim3(256), 0, s, a, rows);
-    else hipLaunchKernelGGL((gemm_tn_kernel<BMODE, 2, 1>), grid, dim3(256), 0, s, a, rows);
-  } else {
-    if (TB == 128) hipLaunchKernelGGL((gemm_tn_kernel<BMODE, 0, 0>), grid, dim3(256), 0, s, a, rows);
-    else if (TB == 64) hipLaunchKernelGGL((gemm_tn_kernel<BMODE, 1, 0>), grid, dim3(256), 0, s, a, rows);
-    else hipLaunchKernelGGL((gemm_tn_kernel<BMODE, 2, 0>), grid, dim3(256), 0, s, a, rows);
-  }
-  if (!a.defer_reduce) launch_reduce(a, splits, s);  // deferred: the caller sums the partials later, batched with others (spgan_splitk_reduce_multi)
+  } else if (pl.kernel == TN_SKINNY) {
+    const dim3 g(cdiv(pl.narrow_b ? a.Na : a.Nb, 64), pl.splits);
+    if (pl.narrow_b) hipLaunchKernelGGL((gemm_tn_skinny_kernel<true>), g, dim3(256), 0, s, a, pl.rows);
+    else hipLaunchKernelGGL((gemm_tn_skinny_kernel<false>), g, dim3(256), 0, s, a, pl.rows);
+  } else if (pl.tile_b == 128) launch_tn_tile<BMODE, 0>(a, pl, s);
+  else if (pl.tile_b == 64) launch_tn_tile<BMODE, 1>(a, pl, s);
+  else launch_tn_tile<BMODE, 2>(a, pl, s);
+  if (!a.defer_reduce) launch_reduce(a, pl.splits, s);  // deferred: the caller sums the partials later, batched with others (spgan_splitk_reduce_multi)
   if constexpr (BMODE != SPGAN_A_EDGE) {
-    if (a.a_sp_val) hipLaunchKernelGGL((tn_sparse_rows_kernel<BMODE>), dim3(a.Na), dim3(256), 0, s, a);
+    if (pl.sparse_rows) hipLaunchKernelGGL((tn_sparse_rows_kernel<BMODE>), dim3(a.Na), dim3(256), 0, s, a);
   }
   return spgan_launch_status();
 }
@@ -2176,32 +2124,19 @@ extern "C" int spgan_sparse_rows_tn(const float* val, const int32_t* arg, int B,
   return spgan_launch_status();
 }
 
-extern "C" size_t spgan_gemm_tn_ws_bytes(int M, int Na, int Nb) {
-  if (M <= 0 || Na <= 0 || Nb <= 0) return 0;
-  int splits, rows;
-  tn_plan(M, Na, Nb, &splits, &rows);
-  return (size_t)splits * Na * Nb * sizeof(float);
-}
+// the shape-only queries: the caller sizes ws and the split reduction before it has a block (no positive size: 0)
+extern "C" int spgan_gemm_tn_splits_lp(int M, int Na, int Nb, int mfma_lp) { return tn_split(M, Na, Nb, mfma_lp).splits; }
+extern "C" size_t spgan_gemm_tn_ws_bytes_lp(int M, int Na, int Nb, int mfma_lp) { return (size_t)tn_split(M, Na, Nb, mfma_lp).splits * Na * Nb * sizeof(float); }
+extern "C" int spgan_gemm_tn_splits(int M, int Na, int Nb) { return spgan_gemm_tn_splits_lp(M, Na, Nb, 0); }
+extern "C" size_t spgan_gemm_tn_ws_bytes(int M, int Na, int Nb) { return spgan_gemm_tn_ws_bytes_lp(M, Na, Nb, 0); }
 
-extern "C" int spgan_gemm_tn_splits(int M, int Na, int Nb) {
-  if (M <= 0 || Na <= 0 || Nb <= 0) return 0;
-  int splits, rows;
-  tn_plan(M, Na, Nb, &splits, &rows);
-  return splits;
-}
+extern "C" int spgan_gemm_tn_kernel(const spgan_gemm_tn_args* a) { return a ? tn_plan(*a).kernel : 0; }
 
-extern "C" size_t spgan_gemm_tn_ws_bytes_lp(int M, int Na, int Nb, int mfma_lp) {
-  if (M <= 0 || Na <= 0 || Nb <= 0) return 0;
-  int splits, rows;
-  tn_plan_lp(M, Na, Nb, mfma_lp, &splits, &rows);
-  return (size_t)splits * Na * Nb * sizeof(float);
-}
-
-extern "C" int spgan_gemm_tn_splits_lp(int M, int Na, int Nb, int mfma_lp) {
-  if (M <= 0 || Na <= 0 || Nb <= 0) return 0;
-  int splits, rows;
-  tn_plan_lp(M, Na, Nb, mfma_lp, &splits, &rows);
-  return splits;
+extern "C" int spgan_gemm_tn_plan(const spgan_gemm_tn_args* a, int32_t* out) {
+  SPGAN_CHECK_ARG(a && out);
+  const spgan_tn_plan p = tn_plan(*a);
+  memcpy(out, &p, sizeof p);
+  return SPGAN_OK;
 }
 
 extern "C" int spgan_splitk_reduce_blocks(int splits, int Na, int Nb) {
@@ -2224,19 +2159,18 @@ extern "C" int spgan_splitk_reduce_multi(const spgan_splitk_multi_args* a, spgan
 extern "C" int spgan_gemm_tn_skinny_multi(const spgan_gemm_tn_args* a, int count, spgan_stream_t s_) {
   SPGAN_CHECK_ARG(a && count >= 1 && count <= SPGAN_GROUP_MAX);
   TnSkinnyMulti m;
+  const spgan_tn_plan pl = tn_plan(*a);   // one geometry, one operand mode: every block's plan has these splits and rows
   for (int g = 0; g < count; ++g) {
     const spgan_gemm_tn_args& q = a[g];
-    SPGAN_CHECK_ARG(q.A && q.B && q.ws && q.M > 0 && q.M < (1 << 24) && q.Na > 0 && q.Nb > 0 && q.Nb <= 4 && tn_skinny(q.Na, q.Nb));
+    const spgan_tn_plan pg = tn_plan(q);  // the block's stand-alone launch would run the streaming kernel with B as the narrow side
+    SPGAN_CHECK_ARG(q.A && q.B && q.ws && q.M > 0 && q.M < (1 << 24) && q.Na > 0 && q.Nb > 0);
+    SPGAN_CHECK_ARG(pg.kernel == TN_SKINNY && pg.narrow_b && !pg.invalid && q.defer_reduce && !q.a_lrelu && !q.a_sp_val);
     SPGAN_CHECK_ARG(q.M == a[0].M && q.Na == a[0].Na && q.Nb == a[0].Nb && q.lda >= q.Na && q.ldb >= q.Nb);
-    SPGAN_CHECK_ARG(q.b_mode == SPGAN_A_PLAIN && q.defer_reduce && !q.a_colsum_ws && !q.b_half && !q.a_half && !q.a_lrelu && !q.a_sp_val);
-    SPGAN_CHECK_ARG(q.ws_bytes >= spgan_gemm_tn_ws_bytes(q.M, q.Na, q.Nb));
+    SPGAN_CHECK_ARG(q.ws_bytes >= (size_t)pg.splits * q.Na * q.Nb * sizeof(float));
     if (q.A2) SPGAN_CHECK_ARG(q.a_scale && q.a_scale2 && q.a_shift && q.lda2 >= q.Na);
-    else SPGAN_CHECK_ARG(!q.a_scale);
     m.a[g] = q;
   }
-  int splits, rows;
-  tn_plan(a->M, a->Na, a->Nb, &splits, &rows);
-  hipLaunchKernelGGL(gemm_tn_skinny_multi_kernel, dim3(cdiv(a->Na, 64), splits, count), dim3(256), 0, (hipStream_t)s_, m, rows);
+  hipLaunchKernelGGL(gemm_tn_skinny_multi_kernel, dim3(cdiv(a->Na, 64), pl.splits, count), dim3(256), 0, (hipStream_t)s_, m, pl.rows);
   return spgan_launch_status();
 }
 
@@ -2245,19 +2179,20 @@ extern "C" int spgan_gemm_tn(const spgan_gemm_tn_args* a, spgan_stream_t s_) {
   SPGAN_CHECK_ARG(a && !(a->defer_reduce && a->a_sp_val));
   SPGAN_CHECK_ARG(a && a->A && a->B && a->C && a->ws && a->M > 0 && a->Na > 0 && a->Nb > 0);
   SPGAN_CHECK_ARG(a->lda >= a->Na && a->ldb >= a->Nb && a->ldc >= a->Nb);
-  SPGAN_CHECK_ARG(a->ws_bytes >= spgan_gemm_tn_ws_bytes_lp(a->M, a->Na, a->Nb, a->mfma_lp));
+  const spgan_tn_plan pl = tn_plan(*a);   // the kernel and the split this block runs (reads no memory)
+  SPGAN_CHECK_ARG(a->ws_bytes >= (size_t)pl.splits * a->Na * a->Nb * sizeof(float));
   if (a->b_mode != SPGAN_A_PLAIN) SPGAN_CHECK_ARG(a->p_scale && a->p_shift);
   if (a->a_scale) SPGAN_CHECK_ARG(a->a_shift && (!a->a_sp_val || (a->a_sp_arg && a->a_sp_rows > 0 && a->b_mode != SPGAN_A_EDGE)));
   if (a->A2) SPGAN_CHECK_ARG(a->a_scale && a->a_scale2 && !a->a_sp_val && a->lda2 >= a->Na);
   if (a->a_lrelu) SPGAN_CHECK_ARG(a->a_scale && !a->A2 && !a->a_sp_val);
   if (a->a_colsum_ws) SPGAN_CHECK_ARG(!a->a_sp_val);  // (a streaming-shaped problem with this by-product runs on the MFMA kernel)
   SPGAN_CHECK_ARG(a->M < (1 << 24));  // fast_div domain
+  if (a->b_mode == SPGAN_A_EDGE) SPGAN_CHECK_ARG(a->e_idx && a->e_bias && a->e_k > 0);
+  SPGAN_CHECK_ARG(!pl.invalid);
   switch (a->b_mode) {
-    case SPGAN_A_PLAIN: return launch_tn<SPGAN_A_PLAIN>(*a, s);
-    case SPGAN_A_AFFINE_LRELU: return launch_tn<SPGAN_A_AFFINE_LRELU>(*a, s);
-    case SPGAN_A_EDGE:
-      SPGAN_CHECK_ARG(a->e_idx && a->e_bias && a->e_k > 0);
-      return launch_tn<SPGAN_A_EDGE>(*a, s);
+    case SPGAN_A_PLAIN: return launch_tn<SPGAN_A_PLAIN>(*a, pl, s);
+    case SPGAN_A_AFFINE_LRELU: return launch_tn<SPGAN_A_AFFINE_LRELU>(*a, pl, s);
+    case SPGAN_A_EDGE: return launch_tn<SPGAN_A_EDGE>(*a, pl, s);
     default: return SPGAN_EINVAL;
   }
 }

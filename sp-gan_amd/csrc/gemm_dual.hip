@@ -365,43 +365,41 @@ __global__ __launch_bounds__(2 * NA, NA == 128 ? 2 : 1) void gemm_dual_multi_ker
 }
 
 // row run -> workgroup plan.  Na = 128: two workgroups per CU resident (LDS) -> 512 slots; Na = 256: one -> 256 slots; the slots are shared
-// by the column parts of a run; at least 4 chunks per run to amortise the W load and the partial store
-inline void dual_plan(int M, int Na, int Nb, int* runs, int* cpw) {
-  const int chunks = M / R, parts = Nb / NBW;
-  const int slots = (Na == 128 ? 512 : 256) / parts;
-  int per = (chunks + slots - 1) / slots;
-  if (per < 4) per = 4;
-  *cpw = per;
-  *runs = (chunks + per - 1) / per;
-}
-
-inline bool dual_shape_ok(int M, int Na, int Nb, int e_k) {
-  if (M < 8192 || M % R) return false;
-  if (Na == 128 && Nb == 64) return e_k == 0 || e_k == 10;
-  if (Na == 256 && (Nb == 128 || Nb == 256)) return e_k == 0;
-  return false;
+// by the column parts of a run; at least 4 chunks per run to amortise the W load and the partial store.
+// ok: a shape the kernels run (launches, spgan_gemm_dual_wgs).  spgan_gemm_dual_rows_per_wg answers on the WIDER set for which the other
+// fields are filled (any M >= 32, Na 128 / 256, Nb a multiple of 64), as it always has; elsewhere everything is 0.
+struct DualPlan {
+  bool ok;
+  int runs, cpw, parts, grid1, threads;   // cpw: chunks of R rows per run; grid1: workgroups of one problem (a multiple of 8: one XCD map)
+};
+inline DualPlan dual_plan(int M, int Na, int Nb, int e_k) {
+  DualPlan p = {};
+  if (M < R || !(Na == 128 || Na == 256) || Nb < NBW || Nb % NBW) return p;
+  if (M >= 8192 && M % R == 0) p.ok = (Na == 128 && Nb == 64) ? (e_k == 0 || e_k == 10) : (Na == 256 && (Nb == 128 || Nb == 256) && e_k == 0);
+  const int chunks = M / R;
+  p.parts = Nb / NBW;
+  const int slots = (Na == 128 ? 512 : 256) / p.parts;
+  p.cpw = (chunks + slots - 1) / slots;
+  if (p.cpw < 4) p.cpw = 4;
+  p.runs = (chunks + p.cpw - 1) / p.cpw;
+  p.grid1 = ((p.runs * p.parts + 7) / 8) * 8;
+  p.threads = 2 * Na;
+  return p;
 }
 
 }  // namespace
 
 extern "C" int spgan_gemm_dual_wgs(int M, int Na, int Nb, int e_k) {
-  if (!dual_shape_ok(M, Na, Nb, e_k)) return 0;
-  int runs, cpw;
-  dual_plan(M, Na, Nb, &runs, &cpw);
-  return runs;
+  const DualPlan pl = dual_plan(M, Na, Nb, e_k);
+  return pl.ok ? pl.runs : 0;
 }
 
-extern "C" int spgan_gemm_dual_rows_per_wg(int M, int Na, int Nb) {
-  if (M < R || !(Na == 128 || Na == 256) || Nb < NBW || Nb % NBW) return 0;
-  int runs, cpw;
-  dual_plan(M, Na, Nb, &runs, &cpw);
-  return cpw * R;
-}
+extern "C" int spgan_gemm_dual_rows_per_wg(int M, int Na, int Nb) { return dual_plan(M, Na, Nb, 0).cpw * R; }
 
 static int dual_check(const spgan_gemm_dual_args* a) {
   SPGAN_CHECK_ARG(a && a->A && a->W && a->B && a->G && a->stats && a->ws && a->b_scale && a->b_shift && a->b_mean && a->b_invstd);
   const int ek = a->e_idx ? a->e_k : 0;
-  SPGAN_CHECK_ARG(dual_shape_ok(a->M, a->Na, a->Nb, ek));
+  SPGAN_CHECK_ARG(dual_plan(a->M, a->Na, a->Nb, ek).ok);
   SPGAN_CHECK_ARG(a->a_mode == A_DENSE || a->a_mode == A_LAZY2 || a->a_mode == A_ACT);
   SPGAN_CHECK_ARG(a->a_mode == A_DENSE || (a->p && a->r));
   SPGAN_CHECK_ARG(a->a_mode != A_LAZY2 || (a->A2 && a->q));
@@ -421,17 +419,12 @@ extern "C" int spgan_gemm_dual(const spgan_gemm_dual_args* a, spgan_stream_t s_)
   const int rc = dual_check(a);
   if (rc != SPGAN_OK) return rc;
   const int ek = a->e_idx ? a->e_k : 0;
-  int runs, cpw;
-  dual_plan(a->M, a->Na, a->Nb, &runs, &cpw);
-  const int parts = a->Nb / NBW;
-  const int grid = ((runs * parts + 7) / 8) * 8;
+  const DualPlan pl = dual_plan(a->M, a->Na, a->Nb, ek);
+  const dim3 grid(pl.grid1), block(pl.threads);
   hipStream_t s = (hipStream_t)s_;
-  if (a->Na == 128) {
-    if (ek == 0) hipLaunchKernelGGL((gemm_dual_kernel<0, 128>), dim3(grid), dim3(256), 0, s, *a, cpw, runs, parts, a->a_mode);
-    else hipLaunchKernelGGL((gemm_dual_kernel<10, 128>), dim3(grid), dim3(256), 0, s, *a, cpw, runs, parts, a->a_mode);
-  } else {
-    hipLaunchKernelGGL((gemm_dual_kernel<0, 256>), dim3(grid), dim3(512), 0, s, *a, cpw, runs, parts, a->a_mode);
-  }
+  if (a->Na == 256) hipLaunchKernelGGL((gemm_dual_kernel<0, 256>), grid, block, 0, s, *a, pl.cpw, pl.runs, pl.parts, a->a_mode);
+  else if (ek == 0) hipLaunchKernelGGL((gemm_dual_kernel<0, 128>), grid, block, 0, s, *a, pl.cpw, pl.runs, pl.parts, a->a_mode);
+  else hipLaunchKernelGGL((gemm_dual_kernel<10, 128>), grid, block, 0, s, *a, pl.cpw, pl.runs, pl.parts, a->a_mode);
   return spgan_launch_status();
 }
 
@@ -445,12 +438,10 @@ extern "C" int spgan_gemm_dual_multi(const spgan_gemm_dual_args* a, int count, s
     SPGAN_CHECK_ARG(!a[g].e_idx && a[g].M == a[0].M && a[g].Na == a[0].Na && a[g].Nb == a[0].Nb);   // one geometry, plain pre tensors
     m.a[g] = a[g];
   }
-  int runs, cpw;
-  dual_plan(a->M, a->Na, a->Nb, &runs, &cpw);
-  const int parts = a->Nb / NBW;
-  const int grid1 = ((runs * parts + 7) / 8) * 8;
+  const DualPlan pl = dual_plan(a->M, a->Na, a->Nb, 0);
+  const dim3 grid(pl.grid1 * count), block(pl.threads);
   hipStream_t s = (hipStream_t)s_;
-  if (a->Na == 128) hipLaunchKernelGGL((gemm_dual_multi_kernel<128>), dim3(grid1 * count), dim3(256), 0, s, m, cpw, runs, parts, grid1);
-  else hipLaunchKernelGGL((gemm_dual_multi_kernel<256>), dim3(grid1 * count), dim3(512), 0, s, m, cpw, runs, parts, grid1);
+  if (a->Na == 128) hipLaunchKernelGGL((gemm_dual_multi_kernel<128>), grid, block, 0, s, m, pl.cpw, pl.runs, pl.parts, pl.grid1);
+  else hipLaunchKernelGGL((gemm_dual_multi_kernel<256>), grid, block, 0, s, m, pl.cpw, pl.runs, pl.parts, pl.grid1);
   return spgan_launch_status();
 }

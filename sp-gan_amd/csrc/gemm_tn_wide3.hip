@@ -292,50 +292,15 @@ int launch_apro(const spgan_gemm_tn_args& a, int cfg, int splits, int rows, hipS
 
 template <int BMODE>
 int launch_bmode(const spgan_gemm_tn_args& a, int cfg, int splits, int rows, hipStream_t s) {
-  if (a.A2) return SPGAN_EINVAL;      // not eligible (spgan_tn_wide3_eligible): see there
+  if (a.A2) return SPGAN_EINVAL;      // not eligible (spgan_tn_wide3_eligible, gemm_tn_plan.hpp): see there
   if (a.a_scale) return launch_apro<BMODE, 1>(a, cfg, splits, rows, s);
   return launch_apro<BMODE, 0>(a, cfg, splits, rows, s);
 }
 
 }  // namespace
 
-// Tile configuration (WGM*10 + WGN: output tile 128*WGM x 64*WGN) for an [Na, Nb] weight gradient, 0 when the shape is not this kernel's
-int spgan_tn_wide3_config(int M, int Na, int Nb) {
-  if (M < 64 || M % 32 || Na % 128 || Nb % 128) return 0;
-  const int cfg = (Na % 256 == 0 ? 20 : 10) + (Nb % 256 == 0 ? 4 : 2);
-  return cfg == 12 ? 0 : cfg;      // 128 x 128 tiles (two waves per workgroup): measured slower than the fp32 kernel (38 -> 47 us at 65536 x 128 x 128)
-}
-
-// The split plan of the split-bf16 kernel: one 512-thread workgroup per CU, two 256-thread ones, four 128-thread ones
-void spgan_tn_wide3_plan(int M, int Na, int Nb, int* splits, int* rows) {
-  const int cfg = spgan_tn_wide3_config(M, Na, Nb);
-  const int xm = (cfg / 10) * 128, xn = (cfg % 10) * 64, threads = xm * xn / 128;
-  const int tiles = (Na / xm) * (Nb / xn);
-  const int target = 256 * 512 / threads;
-  int want = cdiv(target, tiles);
-  int r = cdiv(M, want);
-  if (r < 64) r = 64;
-  r = cdiv(r, 32) * 32;
-  *rows = r;
-  *splits = cdiv(M, r);
-}
-
-bool spgan_tn_wide3_eligible(const spgan_gemm_tn_args& a) {
-  auto al4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
-  if (a.mfma_lp != 2 || !spgan_tn_wide3_config(a.M, a.Na, a.Nb)) return false;
-  if (a.b_mode == SPGAN_A_EDGE || a.a_half || a.b_half) return false;
-  // the two-tensor lazy A operand doubles the A quads in flight (8 more registers per quad on top of 128 accumulators): the kernel spills and
-  // measured no faster (65536 x 256 x 256: 112 us) or slower (256 x 128: 212 us against 63) than the fp32 kernel -- it keeps that one
-  if (a.A2) return false;
-  if (!al4(a.A) || !al4(a.B)) return false;
-  if (a.b_mode != SPGAN_A_PLAIN && !(a.p_slope >= 0.f && a.p_slope <= 1.f)) return false;
-  if (a.a_lrelu && !(a.a_slope >= 0.f && a.a_slope <= 1.f)) return false;
-  if ((double)a.M * a.lda >= 4294967296.0 || (double)a.M * a.ldb >= 4294967296.0) return false;
-  return true;
-}
-
-int spgan_launch_tn_wide3(const spgan_gemm_tn_args& a, int splits, int rows, hipStream_t s) {
-  const int cfg = spgan_tn_wide3_config(a.M, a.Na, a.Nb);
+// cfg = WGM*10 + WGN of the plan (gemm_tn_plan.hpp: spgan_tn_wide3_config), splits and rows its split
+int spgan_launch_tn_wide3(const spgan_gemm_tn_args& a, int cfg, int splits, int rows, hipStream_t s) {
   if (a.b_mode == SPGAN_A_PLAIN) return launch_bmode<SPGAN_A_PLAIN>(a, cfg, splits, rows, s);
   return launch_bmode<SPGAN_A_AFFINE_LRELU>(a, cfg, splits, rows, s);
 }

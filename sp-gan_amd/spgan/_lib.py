@@ -28,6 +28,9 @@ class ColTail(C.Structure):
 # spgan_gemm_nt_kernel's answers (SPGAN_NT_KERNEL_* of spgan_hip.h)
 NT_KERNEL_K4_STREAM, NT_KERNEL_SMALL, NT_KERNEL_TILE, NT_KERNEL_WIDE, NT_KERNEL_WIDE16, NT_KERNEL_WIDE3 = 1, 2, 3, 4, 5, 6
 NT_PLAN_FIELDS = ("kernel", "invalid", "tile_n", "owns_columns", "cfg", "db", "fast", "operand", "store16", "wide3_cfg")   # spgan_gemm_nt_plan
+# spgan_gemm_tn_kernel's answers (SPGAN_TN_KERNEL_* of spgan_hip.h)
+TN_KERNEL_SKINNY, TN_KERNEL_TILE, TN_KERNEL_LP, TN_KERNEL_WIDE3 = 1, 2, 3, 4
+TN_PLAN_FIELDS = ("kernel", "invalid", "splits", "rows", "tile_b", "fast", "narrow_b", "wide3_cfg", "sparse_rows")   # spgan_gemm_tn_plan
 
 
 class GemmNTArgs(C.Structure):
@@ -234,6 +237,8 @@ SIGNATURES = {
     "spgan_gemm_tn_ws_bytes_lp": (SZ, [I, I, I, I]),
     "spgan_gemm_tn_splits_lp": (I, [I, I, I, I]),
     "spgan_gemm_tn": (I, [C.POINTER(GemmTNArgs), P]),
+    "spgan_gemm_tn_kernel": (I, [C.POINTER(GemmTNArgs)]),
+    "spgan_gemm_tn_plan": (I, [C.POINTER(GemmTNArgs), P]),
     "spgan_gemm_tn_skinny_multi": (I, [C.POINTER(GemmTNArgs), I, P]),
     "spgan_sparse_rows_nt": (I, [P, P, I, I, I, P, I, I, P, I, P]),
     "spgan_sparse_rows_tn": (I, [P, P, I, I, I, P, I, I, P, P, F, P, I, P]),

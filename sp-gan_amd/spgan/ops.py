@@ -1047,19 +1047,10 @@ TN_SPLIT_BF16 = [os.environ.get("SPGAN_TN_SPLIT", "1") != "0"]
 TN_LP_MIN_ROWS = 8192     # "f16" operand mode: weight gradients reduce over >= this many points/edges on the bf16 matrix pipe
 
 
-def gemm_tn(A: Tensor, Bm: Tensor, *, pro=None, edge=None, out: Optional[Tensor] = None, beta: float = 0.0, defer: bool = False,
-            exact: bool = False, with_colsum: bool = False, a_pro=None):
-    """C[Na,Nb] = beta*C + A^T @ pro(Bm): weight gradient, reduction over the M rows (points or edges).
-    A may be a SparseAffine operand (evaluated on load).
-    In the "f16" operand mode (set_mfma_operands) the products that reduce over the points / edges (M >= TN_LP_MIN_ROWS) round
-    both operands to bfloat16 at the LDS staging -- fp32's exponent range: per-point gradients are 1e-5..1e-8 -- and accumulate in
-    fp32 (spgan_gemm_tn_args.mfma_lp); the small weight-by-weight products and exact=True calls keep fp32 operands.
-    defer=True: the returned tensor is NOT valid until flush_tn() ran -- the split-K partial sums of all the weight gradients of a
-    backward pass are then finished by one launch (functions._deliver flushes before it hands gradients on).
-    a_pro = (scale [Na], shift [Na], slope): the A operand is lrelu(A*scale + shift, slope), evaluated on load (plain A only).
-    with_colsum=True: -> (C, colsum(A) [Na]): the column sums of the (transformed) A operand -- the bias gradient that belongs to this
-    weight gradient -- come out of the same launch (spgan_gemm_tn_args.a_colsum_ws) and are finished by the same split reduction
-    (deferred like C with defer=True) instead of a colsum pass of their own."""
+def _tn_block(A, Bm, *, pro=None, edge=None, out=None, beta=0.0, defer=False, exact=False, a_pro=None):
+    """The spgan_gemm_tn_args block of gemm_tn(A, Bm, ...), filled but for the a_colsum_ws by-product: the A operand (a dense tensor, Affine2 or
+    SparseAffine), B and its prologue, out / beta, the geometry, the operand mode and the workspace of the block's plan.
+    -> (block, plan as a dict over _lib.TN_PLAN_FIELDS, the A tensor, out, beta, ws)"""
     sa = A if isinstance(A, SparseAffine) else None
     a2 = A if isinstance(A, Affine2) else None
     if sa is not None:
@@ -1082,6 +1073,7 @@ def gemm_tn(A: Tensor, Bm: Tensor, *, pro=None, edge=None, out: Optional[Tensor]
     Nb = Bm.shape[1]
     a = GemmTNArgs()
     a.b_half = 1 if b_half else 0
+    a.a_half = 1 if a16 else 0
     if a2 is not None:
         a.a_scale = _p(_vec(a2.p, Na, "p")); a.a_shift = _p(_vec(a2.r, Na, "r"))
         a.A2 = _p(a2.y); a.lda2 = _ld(a2.y); a.a_scale2 = _p(_vec(a2.q, Na, "q"))
@@ -1111,39 +1103,62 @@ def gemm_tn(A: Tensor, Bm: Tensor, *, pro=None, edge=None, out: Optional[Tensor]
         beta = 0.0
     else:
         _rowmajor2d(out, "out")
-    lib = _lib.load()
     a.mfma_lp = 1 if (_MFMA_F16[0] == 1 and not exact and M_ >= TN_LP_MIN_ROWS) else 0
     if _MFMA_F16[0] == 2 and TN_SPLIT_BF16[0] and not exact and M_ >= TN_LP_MIN_ROWS:
         a.mfma_lp = 2                   # split-bf16 weight gradient (see TN_SPLIT_BF16)
     if (b_half or a16) and a.mfma_lp != 1:
         raise ValueError("16-bit stored operands need the bf16 weight-gradient kernel ('f16' operand mode, M >= %d, exact=False)" % TN_LP_MIN_ROWS)
-    wsb = lib.spgan_gemm_tn_ws_bytes_lp(M_, Na, Nb, a.mfma_lp)       # (the split-bf16 kernel has its own split plan)
-    ws = torch.empty((wsb // 4,), dtype=torch.float32, device=A.device)
     a.A = _p(A); a.lda = _ld(A); a.B = _p(Bm); a.ldb = _ld(Bm); a.C = _p(out); a.ldc = _ld(out)
     a.M, a.Na, a.Nb = M_, Na, Nb
-    a.beta = float(beta); a.ws = _p(ws); a.ws_bytes = wsb
-    defer = bool(defer) and sa is None
-    a.defer_reduce = 1 if defer else 0
-    a.a_half = 1 if a16 else 0
-    splits = lib.spgan_gemm_tn_splits_lp(M_, Na, Nb, a.mfma_lp)
-    cs_out = cs_ws = None
-    streaming = (Na <= 4 or Nb <= 4) and Na <= 2048 and Nb <= 2048 and pro is None and edge is None and sa is None and a_pro is None and (a2 is None or Nb <= 4)   # 3-column layers: the streaming kernel + a colsum pass stay cheaper (mirrors launch_tn: a narrow-A two-tensor operand runs on the MFMA kernel)
-    if with_colsum and sa is not None:
+    a.beta = float(beta)
+    a.defer_reduce = 1 if (defer and sa is None) else 0
+    # the one decision of the library (csrc/gemm_tn_plan.hpp): the kernel, and the split that sizes the workspace
+    ints = (C.c_int32 * len(_lib.TN_PLAN_FIELDS))()
+    check(_lib.load().spgan_gemm_tn_plan(C.byref(a), ints), "gemm_tn_plan", M=M_, Na=Na, Nb=Nb)
+    plan = dict(zip(_lib.TN_PLAN_FIELDS, ints))
+    a.ws_bytes = plan["splits"] * Na * Nb * 4
+    ws = torch.empty((plan["splits"] * Na * Nb,), dtype=torch.float32, device=A.device)
+    a.ws = _p(ws)
+    return a, plan, A, out, float(beta), ws
+
+
+def gemm_tn(A: Tensor, Bm: Tensor, *, pro=None, edge=None, out: Optional[Tensor] = None, beta: float = 0.0, defer: bool = False,
+            exact: bool = False, with_colsum: bool = False, a_pro=None):
+    """C[Na,Nb] = beta*C + A^T @ pro(Bm): weight gradient, reduction over the M rows (points or edges).
+    A may be a SparseAffine operand (evaluated on load).
+    In the "f16" operand mode (set_mfma_operands) the products that reduce over the points / edges (M >= TN_LP_MIN_ROWS) round
+    both operands to bfloat16 at the LDS staging -- fp32's exponent range: per-point gradients are 1e-5..1e-8 -- and accumulate in
+    fp32 (spgan_gemm_tn_args.mfma_lp); the small weight-by-weight products and exact=True calls keep fp32 operands.
+    defer=True: the returned tensor is NOT valid until flush_tn() ran -- the split-K partial sums of all the weight gradients of a
+    backward pass are then finished by one launch (functions._deliver flushes before it hands gradients on).
+    a_pro = (scale [Na], shift [Na], slope): the A operand is lrelu(A*scale + shift, slope), evaluated on load (plain A only).
+    with_colsum=True: -> (C, colsum(A) [Na]): the column sums of the (transformed) A operand -- the bias gradient that belongs to this
+    weight gradient -- come out of the same launch (spgan_gemm_tn_args.a_colsum_ws) and are finished by the same split reduction
+    (deferred like C with defer=True) instead of a colsum pass of their own."""
+    if with_colsum and isinstance(A, SparseAffine):
         raise NotImplementedError("gemm_tn(with_colsum=True) with a SparseAffine operand")
-    if with_colsum and not streaming:
+    operand = A
+    a, plan, A, out, beta, ws = _tn_block(A, Bm, pro=pro, edge=edge, out=out, beta=beta, defer=defer, exact=exact, a_pro=a_pro)
+    M_, Na, Nb, splits = a.M, a.Na, a.Nb, plan["splits"]
+    defer = bool(a.defer_reduce)
+    cs_out = cs_ws = None
+    # The by-product rides in the launch unless the block runs the streaming kernel (3-column layers: that kernel + a colsum pass stay
+    # cheaper).  Asked BEFORE a_colsum_ws is attached: a block that carries it never runs the streaming kernel.
+    if with_colsum and plan["kernel"] != _lib.TN_KERNEL_SKINNY:
         cs_ws = torch.empty((splits, Na), dtype=torch.float32, device=A.device)
         cs_out = torch.empty((Na,), dtype=torch.float32, device=A.device)
         a.a_colsum_ws = _p(cs_ws)
+    lib = _lib.load()
     done = launch_timer("gemm_tn", a) if launch_timer is not None else None
     check(lib.spgan_gemm_tn(C.byref(a), _s()), "gemm_tn", M=M_, Na=Na, Nb=Nb)
     if done is not None:
         done()
     if defer:
-        _PENDING_TN.append((ws, out, splits, Na, Nb, _ld(out), float(beta)))
+        _PENDING_TN.append((ws, out, splits, Na, Nb, _ld(out), beta))
     if not with_colsum:
         return out
     if cs_ws is None:                       # the streaming kernels have no such by-product: the separate reduction (of the TRANSFORMED operand)
-        return out, colsum(a2.dense() if a2 is not None else A)[0]
+        return out, colsum(operand.dense() if isinstance(operand, Affine2) else A)[0]
     _PENDING_TN.append((cs_ws, cs_out, splits, 1, Na, Na, 0.0))           # [splits][1 x Na] partials: one more entry of the multi-reduce
     if not defer:
         flush_tn()
@@ -1156,38 +1171,18 @@ def gemm_tn_narrow_multi(specs):
     -> the list of result tensors (valid after flush_tn(), like gemm_tn(defer=True)), bit-identical to the separate calls."""
     if len(specs) == 1 or not GROUPED[0] or _MFMA_F16[0] == 1:
         return [gemm_tn(sp["A"], sp["Bm"], out=sp.get("out"), beta=sp.get("beta", 0.0), defer=True) for sp in specs]
-    lib = _lib.load()
     n = len(specs)
     arr = (GemmTNArgs * n)()
-    res, keep, pend = [], [], []
+    res, pend = [], []
     for i, sp in enumerate(specs):
-        A, Bm, out, beta = sp["A"], sp["Bm"], sp.get("out"), float(sp.get("beta", 0.0))
-        a2 = A if isinstance(A, Affine2) else None
-        if a2 is not None:
-            if a2.half:
-                raise ValueError("gemm_tn_narrow_multi: fp32 operands")
-            A = a2.g
-        _rowmajor2d(A, "A"); _rowmajor2d(Bm, "B")
-        M_, Na = A.shape
-        Nb = Bm.shape[1]
-        if Bm.shape[0] != M_ or Nb > 4:
-            raise ValueError("gemm_tn_narrow_multi: Bm [M, <= 4]")
-        a = arr[i]
-        if a2 is not None:
-            a.a_scale = _p(_vec(a2.p, Na, "p")); a.a_shift = _p(_vec(a2.r, Na, "r"))
-            a.A2 = _p(a2.y); a.lda2 = _ld(a2.y); a.a_scale2 = _p(_vec(a2.q, Na, "q"))
-        if out is None:
-            out, beta = torch.empty((Na, Nb), dtype=torch.float32, device=A.device), 0.0
-        else:
-            _rowmajor2d(out, "out")
-        wsb = lib.spgan_gemm_tn_ws_bytes(M_, Na, Nb)
-        ws = torch.empty((wsb // 4,), dtype=torch.float32, device=A.device)
-        a.A = _p(A); a.lda = _ld(A); a.B = _p(Bm); a.ldb = _ld(Bm); a.C = _p(out); a.ldc = _ld(out)
-        a.M, a.Na, a.Nb = M_, Na, Nb
-        a.beta = beta; a.ws = _p(ws); a.ws_bytes = wsb; a.defer_reduce = 1; a.b_mode = A_PLAIN
-        pend.append((ws, out, lib.spgan_gemm_tn_splits(M_, Na, Nb), Na, Nb, _ld(out), beta))
+        if (isinstance(sp["A"], Affine2) and sp["A"].half) or sp["Bm"].dim() != 2 or sp["Bm"].shape[1] > 4:
+            raise ValueError("gemm_tn_narrow_multi: fp32 operands, Bm [M, <= 4]")
+        # exact: the streaming kernel has fp32 operands in every operand mode
+        a, plan, _, out, beta, ws = _tn_block(sp["A"], sp["Bm"], out=sp.get("out"), beta=sp.get("beta", 0.0), defer=True, exact=True)
+        arr[i] = a
+        pend.append((ws, out, plan["splits"], a.Na, a.Nb, _ld(out), beta))
         res.append(out)
-    check(lib.spgan_gemm_tn_skinny_multi(arr, n, _s()), "gemm_tn_skinny_multi", count=n)
+    check(_lib.load().spgan_gemm_tn_skinny_multi(arr, n, _s()), "gemm_tn_skinny_multi", count=n)
     _PENDING_TN.extend(pend)
     return res
 
