@@ -38,6 +38,9 @@ def main():
     ap.add_argument("--gan", default="ls"); ap.add_argument("--gp", action="store_true")
     ap.add_argument("--lr_g", type=float, default=1e-4); ap.add_argument("--lr_d", type=float, default=1e-4)
     ap.add_argument("--augment", action="store_true"); ap.add_argument("--epochs", type=int, default=1)
+    ap.add_argument("--augment_set", choices=("ref", "full"), default=None,
+                    help="augment every batch in one call of the device-side kernel (spgan.augment): 'ref' = point shuffle, rotation about y "
+                         "and scale as --augment; 'full' = the reference's point_transform (H5DataLoader.py:21-31) on top of the shuffle")
     ap.add_argument("--out", default="runs/spgan"); ap.add_argument("--choice", default="chair")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--mfma", choices=("f32", "f16", "bf16x3"), default="f32", help="operand mode of the matrix products (INTEGRATION.md section 4a)")
@@ -58,7 +61,8 @@ def main():
     dev = torch.device("cuda", 0)
     torch.manual_seed(123)                                     # model.py:38-41
     src = a.data if a.data else torch.cat([fr.synthetic_real(64, a.np, seed=i) for i in range((a.synthetic + 63) // 64)])[:a.synthetic or 64]
-    data = DeviceDataset(src, num_points=a.np, batch_size=a.bs, scale=a.scale, augment=a.augment, device=dev, seed=0)
+    transform = spgan.augment.reference_transform(a.augment_set, seed=0, device=dev) if a.augment_set else None
+    data = DeviceDataset(src, num_points=a.np, batch_size=a.bs, scale=a.scale, augment=a.augment, device=dev, seed=0, transform=transform)
     G, D = spgan.Generator(Opts).to(dev), spgan.Discriminator(Opts, num_point=a.np).to(dev)
     step = spgan.TrainStep(G, D, gan=a.gan, use_gp=a.gp, lr_g=a.lr_g, lr_d=a.lr_d, graph=not a.no_graph,
                            ema_rate=a.ema_rate if a.ema else None, ema_warmup=a.ema_warmup)

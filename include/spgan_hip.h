@@ -1557,6 +1557,69 @@ int spgan_match_cost_dense_fwd(const float* xyz1, const float* xyz2, const float
 int spgan_match_cost_dense_bwd(const float* xyz1, const float* xyz2, const float* match, int B, int n, int m, const float* grad_cost,
                                float* grad_xyz1, float* grad_xyz2, spgan_stream_t s);
 
+/* ----------------------------------------------------------------------------------------
+ * Device-side batch augmentation (Common/data_utils.py, provider.py, point_operation.py; csrc/augment.hip).
+ * One batch per call, two launches, no host synchronisation, no atomics; results repeat bit for bit.
+ *
+ * data [S,P,C] float32, C = 3 or 6 (xyz + normal); index int64 [B] (an entry outside 0..S-1 yields a cloud of NaN); 1 <= N <= P,
+ * N <= spgan_augment_max_points() = 8192 (any value); B < 2^24.  out: layout 0 [B,N,C], layout 1 [B,C,N].  rec float32 [B,16] per cloud:
+ *   rec[0..8] A row-major, rec[9..11] t, rec[12] the dropout ratio, rec[13], rec[14] the low and high 32 bits of the step value used
+ *   (raw bit patterns, not numbers), rec[15] = 0.  Row-vector convention: xyz' = xyz A + t, i.e. xyz'[c] = sum_r xyz[r] * A[3r + c] + t[c].
+ *
+ * Random numbers: Philox4x32-10 (Salmon et al., SC'11; multipliers D2511F53 / CD9E8D57 on counter words 0 / 2, key increments 9E3779B9 /
+ * BB67AE85, ten rounds).  key = (seed & 0xffffffff, seed >> 32); counter = (e, (purpose << 24) | b, step & 0xffffffff, step >> 32) with
+ * b the slot in the batch.  X(purpose, b, e) are the four output words x0..x3; the WORD STREAM of (purpose, b) is word w = X(purpose, b,
+ * w >> 2)[w & 3] (spgan_philox_fill writes it).  u(x) = (x >> 8) * 2^-24 in [0,1).  n(xa, xb) is the Box-Muller pair
+ * r = sqrtf(-2 logf(((xa >> 8) + 1) * 2^-24)), th = 6.2831853f * u(xb): (r cosf(th), r sinf(th)), accurate library functions.
+ * Draw assignment (every draw exists whether or not its stage is on, so switching a stage never moves another stage's draws):
+ *   purpose 0, per cloud:  e = 0: x0, x1, x2 -> rotation angles a = 6.2831853f * u (axis mode uses x0 only; full mode x0, x1, x2 about
+ *                                  x, y, z); x3 -> dropout ratio = u(x3) * dropout_max (one float32 product)
+ *                          e = 1: perturbation: (g0, g1) = n(x0, x1), (g2, -) = n(x2, x3); angles clip(sigma * g, -clip, clip) about x, y, z
+ *                          e = 2: scale lo + (hi - lo) * u: x0 (one for all axes), or x0, x1, x2 (per axis)
+ *                          e = 3: translation (2 u - 1) * range: x0, x1, x2 (per axis), or x0 added to all three (scalar)
+ *   purpose 1, permutation: point i's 32-bit draw is word i of the stream
+ *   purpose 2, jitter:      point i, e = i: (jx, jy) = n(x0, x1), (jz, -) = n(x2, x3); xyz += clip(sigma * j, -clip, clip)
+ *   purpose 3, dropout:     point i's u is u(word i of the stream); the row is dropped where u <= ratio (float32 compare)
+ *   (purpose 4 is the host-side epoch order of spgan.dataset.DeviceDataset: stream of slot 0 with the epoch in place of step.)
+ *
+ * Stages in this fixed order, each on or off:
+ *   1 gather      row i of cloud b is data[index[b]][i], i < N (the first N stored points)
+ *   2 permute     output row i is gathered row perm[i], perm = the point indices in ascending order of the 64-bit keys
+ *                 (draw << 32) | index; `keys` uint32 [B,N] (optional) replaces the draws.  Sorted in LDS, one workgroup per cloud.
+ *   3 rotate      1: about `axis` (unit vector u; R = c I + s [u]x + (1 - c) u u^T, data_utils.angle_axis); 2: R = Rz Ry Rx
+ *   4 perturb     R = Rz Ry Rx of the three clipped normal angles
+ *                 with Rx = [1 0 0; 0 c -s; 0 s c], Ry = [c 0 s; 0 1 0; -s 0 c], Rz = [c -s 0; s c 0; 0 0 1] (provider.py).
+ *                 A rotation multiplies as xyz @ R (transpose = 0: provider, point_operation) or xyz @ R^T (transpose = 1: data_utils)
+ *   5 scale       xyz * s (one s, or one per axis)
+ *   6 translate   xyz + t
+ *   7 jitter, 8 dropout as above; a dropped row takes the FINAL value (all C channels) of output row 0 of its cloud.
+ *   Stages 3-6 are composed once per cloud in float32, A = M3 M4 diag(s) (M = R or R^T; an absent stage is the identity) and t, and applied
+ *   as xyz A + t; with all four off and no `params`, xyz passes through bit for bit.  Normals (C = 6) are multiplied by A with every column
+ *   divided by its Euclidean norm (= M3 M4 when s > 0): rotated, neither scaled, translated nor jittered.
+ *   params float32 [B,16] (optional) replaces stages 3-6: A, t are taken from it (apply-only mode; slots 12..15 are ignored).
+ *
+ * step: device-resident counter.  The first launch (one workgroup per cloud: parameters, record, sort) reads it and stores its value in
+ * the record; the second launch (one thread per output row) takes the value from the record, and its first thread stores step + 1 when
+ * `advance` != 0 -- after every reader, by the order of the two launches on the stream.  The wrapper passes advance = 1 whenever the call
+ * draws anything.  perm_ws: int32 [B,N] scratch, needed when permute != 0.
+ * Bad sizes, C other than 3 or 6, N beyond the limit and null pointers return SPGAN_EINVAL before any launch.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct spgan_augment_cfg {
+  int permute;                                           /* 0 / 1 */
+  int rotate; float axis[3]; int transpose;              /* 0 off, 1 about axis (unit length), 2 full Rz Ry Rx */
+  int perturb; float perturb_sigma, perturb_clip;        /* 0 / 1 */
+  int scale; float scale_lo, scale_hi;                   /* 0 off, 1 one factor, 2 one per axis */
+  int translate; float translate_range;                  /* 0 off, 1 one per axis, 2 one scalar for all three */
+  int jitter; float jitter_sigma, jitter_clip;           /* 0 / 1 */
+  int dropout; float dropout_max;                        /* 0 / 1 */
+} spgan_augment_cfg;
+int spgan_augment_max_points(void);
+int spgan_augment_batch(const float* data, long S, int P, int C, const int64_t* index, int B, int N, int layout, const spgan_augment_cfg* cfg,
+                        unsigned long long seed, unsigned long long* step, int advance, const uint32_t* keys, const float* params,
+                        int32_t* perm_ws, float* out, float* rec, spgan_stream_t s);
+/* out[w] = word w of the stream of (purpose, slot) at `step` under `seed`, w < n_words; purpose < 256, slot < 2^24. */
+int spgan_philox_fill(unsigned long long seed, int purpose, int slot, unsigned long long step, long n_words, uint32_t* out, spgan_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

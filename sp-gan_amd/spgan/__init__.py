@@ -7,7 +7,8 @@ Importing the package does not touch the GPU; the shared library is loaded on fi
 absence is a hard error (there is no CPU fallback).
 """
 from . import block_tail, dataset, edge_conv, edge_max, edge_rank, edge_weight, edge_window, fixture_rng, metrics, ops, pointconv_util, pointnet_util, point_attn, gc_attn, sampling  # noqa: F401
-from . import approxmatch, compat, fpd, pointops                           # noqa: F401
+from . import approxmatch, augment, compat, fpd, pointops                  # noqa: F401
+from .augment import BatchAugment                                          # noqa: F401
 from .approxmatch import MatchCostFunction, approx_match, emd_approx_match, match_cost, match_cost_dense   # noqa: F401
 from . import pointnet2_modules, pointnet2_utils, pytorch_utils            # noqa: F401
 from .capture import CapturedBody                                          # noqa: F401
@@ -44,4 +45,5 @@ __all__ = ["Generator", "Discriminator", "EdgeBlock", "AdaptivePointNorm", "get_
            "Truncation",
            "model_utils", "get_repulsion_loss", "get_repulsion_loss4", "get_perulsion_loss", "get_uniform_loss_knn", "get_cd_loss", "get_cd_loss2",
            "get_hausdorff_loss", "group_nearest", "get_emd_loss",
-           "approxmatch", "MatchCostFunction", "approx_match", "match_cost", "match_cost_dense", "emd_approx_match"]
+           "approxmatch", "MatchCostFunction", "approx_match", "match_cost", "match_cost_dense", "emd_approx_match",
+           "augment", "BatchAugment"]

@@ -204,6 +204,16 @@ class EpilogueArgs(C.Structure):
                 ("rs", C.c_void_p), ("stat", C.c_void_p), ("rec", C.c_void_p)]
 
 
+class AugmentCfg(C.Structure):
+    """spgan_augment_cfg"""
+    _fields_ = [("permute", C.c_int), ("rotate", C.c_int), ("axis", C.c_float * 3), ("transpose", C.c_int),
+                ("perturb", C.c_int), ("perturb_sigma", C.c_float), ("perturb_clip", C.c_float),
+                ("scale", C.c_int), ("scale_lo", C.c_float), ("scale_hi", C.c_float),
+                ("translate", C.c_int), ("translate_range", C.c_float),
+                ("jitter", C.c_int), ("jitter_sigma", C.c_float), ("jitter_clip", C.c_float),
+                ("dropout", C.c_int), ("dropout_max", C.c_float)]
+
+
 I, F, P, SZ = C.c_int, C.c_float, C.c_void_p, C.c_size_t
 LG, GCB = C.c_long, C.POINTER(GcBranch)
 
@@ -493,6 +503,9 @@ SIGNATURES = {
     "spgan_approxmatch_plan": (I, [P, LG, P, I, I, I, P, P, P, P]),
     "spgan_match_cost_dense_fwd": (I, [P, P, P, I, I, I, P, P, SZ, P]),
     "spgan_match_cost_dense_bwd": (I, [P, P, P, I, I, I, P, P, P, P]),
+    "spgan_augment_max_points": (I, []),
+    "spgan_augment_batch": (I, [P, LG, I, I, P, I, I, I, C.POINTER(AugmentCfg), C.c_ulonglong, P, I, P, P, P, P, P, P]),
+    "spgan_philox_fill": (I, [C.c_ulonglong, I, I, C.c_ulonglong, LG, P, P]),
 }
 
 _lib = None

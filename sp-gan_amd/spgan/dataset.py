@@ -75,10 +75,15 @@ def item_transform(points: Tensor, perm: Tensor, angle_y: Optional[Tensor] = Non
 class DeviceDataset:
     """All shapes of a category in HBM, normalised as H5DataLoader.py:107 (`opts.scale * normalize_point_cloud(data)`).
     Iterating yields `len(self) // bs` batches [bs, np, 3] per epoch in a fresh random order (shuffle=True, drop_last=True),
-    every cloud with its points permuted and, with `augment`, rotated about y and scaled by U[0.8, 1.25]."""
+    every cloud with its points permuted and, with `augment`, rotated about y and scaled by U[0.8, 1.25].
+
+    `transform` (a spgan.augment.BatchAugment; None keeps the path above and its draws bit for bit) makes a batch ONE call of the
+    augmentation kernel, which then does all the per-item work (`augment` is not consulted), and takes the epoch order from the
+    transform's own random stream (purpose 4, keyed by the epoch: sorted on the host once per epoch, one upload).  The state is then
+    (seed, step, epoch, batch) and can be taken between any two batches."""
 
     def __init__(self, source, num_points: int = 2048, batch_size: int = 32, scale: float = 1.0, augment: bool = False,
-                 device="cuda", seed: Optional[int] = None):
+                 device="cuda", seed: Optional[int] = None, transform=None):
         pts = load_points(source, num_points)[:, :, :3]
         if pts.dim() != 3 or pts.shape[1] < num_points:
             raise ValueError("need [S, >=%d, >=3] points, got %s" % (num_points, tuple(pts.shape)))
@@ -90,15 +95,24 @@ class DeviceDataset:
         if seed is not None:
             self.gen.manual_seed(seed)
         self.epoch = 0                                                         # completed passes
+        self.transform = transform
+        self.batch = 0                                                         # batches handed out in the pass in flight (transform only)
 
     def __len__(self) -> int:
         return self.data.shape[0]
 
     def get_state(self) -> dict:
-        """Resume state at an epoch boundary (between two complete passes): the generator's position and the epoch counter."""
+        """Resume state: the generator's position and the epoch counter, valid at an epoch boundary (between two complete passes).
+        With a transform: its seed and step, the epoch and the batches handed out so far -- valid between any two batches."""
+        if self.transform is not None:
+            return {"transform": self.transform.get_state(), "epoch": self.epoch, "batch": self.batch}
         return {"gen": self.gen.get_state(), "epoch": self.epoch}
 
     def set_state(self, state: dict) -> None:
+        if self.transform is not None:
+            self.transform.set_state(state["transform"])
+            self.epoch, self.batch = int(state["epoch"]), int(state["batch"])
+            return
         self.gen.set_state(state["gen"])
         self.epoch = int(state["epoch"])
 
@@ -108,6 +122,8 @@ class DeviceDataset:
 
     def get_batch(self, index: Tensor) -> Tensor:
         """The batch of `__getitem__(i) for i in index` (H5DataLoader.py:113-123)."""
+        if self.transform is not None:
+            return self.transform(self.data, index)[0]
         dev, g = self.device, self.gen
         B, P = index.numel(), self.num_points
         perm = torch.rand((B, P), generator=g, device=dev).argsort(dim=1)      # np.random.shuffle(point_set), per cloud
@@ -118,10 +134,24 @@ class DeviceDataset:
         return item_transform(self.data[index], perm, angle, scale)
 
     def __iter__(self) -> Iterator[Tensor]:
+        if self.transform is not None:
+            yield from self._iter_transform()
+            return
         order = torch.randperm(len(self), generator=self.gen, device=self.device)
         for b in range(self.num_batches):
             yield self.get_batch(order[b * self.batch_size:(b + 1) * self.batch_size])
         self.epoch += 1
+
+    def _iter_transform(self) -> Iterator[Tensor]:
+        """The pass in flight from batch `self.batch` on (0 unless set_state() resumed inside a pass)."""
+        from .augment import epoch_order
+        order = torch.from_numpy(epoch_order(self.transform.seed, self.epoch, len(self))).to(self.device)
+        bs = self.batch_size
+        for b in range(self.batch, self.num_batches):
+            self.batch = b + 1                                                 # the state while the consumer holds batch b
+            yield self.get_batch(order[b * bs:(b + 1) * bs])
+        self.epoch += 1
+        self.batch = 0
 
 
 class HostStagedLoader:
